@@ -9,6 +9,14 @@ FP64, BDF2 with dt = 2.5e-4, synthetic inputs of SURVEY §8d.  One "step" =
 one operator apply (vmult) on inputs already resident in HBM.
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--nref R]
+                       [--dump-outputs DIR] [--full]
+A plain run sets up, settles and warms up, times the K steps and prints the
+result line.  --dump-outputs DIR writes the last timed step's result vector as
+DIR/dst.npy (same arguments, same inputs: two builds compare output for
+output).  --full adds everything else beside the headline: the oracle parity
+gate (exit 3 outside the tolerance), the CPU baseline, the per-vmult event
+pairs and the companion lines (each of them can be left out again with its
+--no-... option).
 For N > 1 launch with torch.distributed.run (one rank per GPU); cells are
 partitioned into contiguous x-slabs, ghost DoFs exchanged over RCCL.
 """
@@ -99,6 +107,25 @@ def cpu_baseline(o, src, n_dofs, budget_s=12.0):
                        f"oracle/gls_cpu_batched.c ({b.isa}, 8 cells per vector, "
                        f"{b.n_colors} batch colours), {el:.1f} s + {el1:.1f} s; "
                        f"agrees with the scalar oracle to {chk:.1e}")
+
+
+DUMP_BYTES = 60_000_000  # per --dump-outputs directory (below 64 MB with the headers)
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy in its own float32 /
+    float64; arrays beyond their share of DUMP_BYTES as a fixed sample
+    (sorted indices drawn without replacement from a generator seeded 0)."""
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        if a.nbytes > share:
+            idx = np.random.default_rng(0).choice(a.size, size=share // a.itemsize, replace=False)
+            a = a.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def _comp_get(comp, key, field):
@@ -754,14 +781,20 @@ def main():
                          "(0: off; reported as 'settle' in the line)")
     ap.add_argument("--nref", type=int, default=None)
     ap.add_argument("--precision", default="f64")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: oracle parity gate, CPU baseline, per-vmult "
+                         "event pairs and the companion lines (off: the timed steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's result vector to DIR/dst.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline")
     ap.add_argument("--no-companions", action="store_true",
-                    help="skip the cold / FP32-level / r+1 companion lines")
+                    help="with --full: skip the cold / FP32-level / r+1 companion lines")
     ap.add_argument("--cpu-budget", type=float, default=15.0)
     ap.add_argument("--brick", default=None,
                     help="cells per brick 'bx,by,bz' (a sub-brick of the mesh order)")
     ap.add_argument("--no-parity", action="store_true",
-                    help="skip the oracle check of the headline result (profiling runs)")
+                    help="with --full: skip the oracle check of the headline result")
     ap.add_argument("--gmres-iteration", action="store_true",
                     help="multi-GPU (or GLS_BENCH_DIST=1): also time the partitioned "
                          "multigrid + GMRES iteration (reported beside the headline)")
@@ -771,6 +804,8 @@ def main():
                     help="multi-GPU: exit 4 when the native RCCL vmult disagrees with the "
                          "torch P2P path (or fails) instead of timing the P2P path")
     args = ap.parse_args()
+    if not args.full:  # a plain run: set up, warm up, time the steps, print the line
+        args.no_parity = args.no_cpu_baseline = args.no_companions = True
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args, sys.argv[1:]))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -958,15 +993,23 @@ def main():
         el = float(t.item())
     ms = el / args.steps * 1e3
     value = n_dofs * args.steps / el
+    if args.dump_outputs:
+        # what the last timed step left in dst (mesh numbering; the partitioned
+        # path gathers the owned entries of every rank: a collective)
+        last = (runner.gather_global(dst) if use_dist else dst).cpu().numpy()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {"dst": last})
+        del last
 
     # average duration of the dominant kernel pair (k_brick + reduce), HIP
     # events on the stream it is launched on (torch's current stream): single
     # GPU, the region events after step 1 / (K - 1) (the vmults back to back,
     # as rocprofv3 sees them); partitioned, the rank-local cell loop between its
     # own events.  kernel_ms_event_pairs: one event pair around each of K more
-    # vmults (the event packets between the launches add ~3 us per vmult)
+    # vmults (the event packets between the launches add ~3 us per vmult;
+    # --full only: a plain partitioned run reports the step's wall time)
     kernel_ms = kernel_ms_pairs = None
-    if kernel_fn is not None:
+    if args.full:
         evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
                for _ in range(args.steps)]
         for e0, e1 in evs:
@@ -1066,6 +1109,8 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            # false: cpu_baseline, parity, companions and the event pairs were not run
+            "full": args.full,
             # untimed steps before the warm-up (the sustained clock, see above)
             "settle": settle,
             "ms_per_step": ms,

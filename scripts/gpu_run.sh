@@ -8,7 +8,8 @@
 # the first failing step ends the run (no GPU step after a failure).  Steps:
 #   tests[:KEXPR[:FILES]]  pytest -m gpu (optionally -k KEXPR, on FILES)
 #   smoke                  __graft_entry__.smoke()
-#   bench[:ARGS]           python bench.py ARGS  -> bench[_N].json
+#   bench[:ARGS]           python bench.py ARGS  -> bench[_N].json (ARGS --full: with
+#                          parity, CPU baseline and the companions printed below)
 #   stats                  rocprofv3 --kernel-trace --stats of the bench command
 #   pmc:f64|f32            PMC passes of the r2 vmult (scripts/gpu_pmc.sh)
 #   ab:FILE                alternating A/B of library variants / environments

@@ -204,8 +204,19 @@ def test_native_group_vcycle_agglomerated(world, prec, coarse, n_ref, k):
 @pytest.mark.parametrize("world", [2, 4])
 def test_native_group_gmres_agglomerated(world):
     """GMRES preconditioned by the agglomerated partitioned multigrid (r0, r1
-    single-domain on every rank, r2 partitioned; FP64 levels, direct coarse
-    solve) against the single-domain solve: iterations +-1, solution 1e-8."""
+    single-domain on every rank, r2 partitioned; FP32 levels, 10 coarse
+    sweeps) against the single-domain solve: iterations +-1 at the relative
+    tolerance 1e-8, solutions 1e-6 apart at 1e-10.
+
+    Two iterates whose residuals are below rho |b| differ by up to
+    2 rho cond(A) |x|, whatever produced them: at rho = 1e-8 the two solves
+    were 1.9e-7 .. 1.1e-6 apart from run to run (the FP32 levels sum with
+    atomics, so the Krylov path and the last residual under the tolerance
+    change between runs), which is the stopping tolerance and not the
+    partitioning.  The solutions are therefore compared after both solves
+    went on to 1e-10, where that term is a hundred times smaller (1e-8
+    measured) and a partitioned preconditioner that differed from the
+    single-domain one would still show against the same 1e-6."""
     import torch
     import glsamd
     import glsdist
@@ -229,8 +240,17 @@ def test_native_group_gmres_agglomerated(world):
     xs = [torch.zeros_like(x) for x in bs]
     res = g.gmres(xs, bs, relative_tolerance=1e-8, absolute_tolerance=0.0)
     torch.cuda.synchronize()
+    err8 = rel_err(g.gather(xs).cpu().numpy(), x_ref.cpu().numpy())
+    x_ref.zero_()
+    solver = glsamd.LinearSolverGMRES(A, mg, relative_tolerance=1e-10, absolute_tolerance=0.0)
+    solver.solve(x_ref, src)
+    xs = [torch.zeros_like(x) for x in bs]
+    res10 = g.gmres(xs, bs, relative_tolerance=1e-10, absolute_tolerance=0.0)
+    torch.cuda.synchronize()
     err = rel_err(g.gather(xs).cpu().numpy(), x_ref.cpu().numpy())
     print(f"world {world} agglomerated: GMRES {res['n_iterations']} vs {it_ref} iterations, "
-          f"x rel diff {err:.2e}")
+          f"x rel diff {err8:.2e} at 1e-8, {err:.2e} at 1e-10 "
+          f"({res10['n_iterations']} vs {solver.last['n_iterations']} iterations)")
     assert res["converged"] and abs(res["n_iterations"] - it_ref) <= 1
+    assert res10["converged"]
     assert err < 1e-6
