@@ -51,7 +51,8 @@ $(LIBDIR)/libglsamd.so: $(AMD_OBJ)
 
 # C++ facade parity program (test infrastructure: links the oracle)
 CPPTEST := tests/cpp/build/test_operator
-cpptest: $(CPPTEST)
+CPPFORCES := tests/cpp/build/test_forces
+cpptest: $(CPPTEST) $(CPPFORCES)
 $(CPPTEST): tests/cpp/test_operator.cc include/gls_operator.hpp include/gls_op.h include/gls_mesh.h \
             $(LIBDIR)/libglsamd.so $(LIBDIR)/libglsmesh.so oracle
 	@mkdir -p tests/cpp/build
@@ -60,8 +61,16 @@ $(CPPTEST): tests/cpp/test_operator.cc include/gls_operator.hpp include/gls_op.h
 	  -Wl,-rpath,'$$ORIGIN/../../../$(LIBDIR)' -Wl,-rpath,'$$ORIGIN/../../../oracle' \
 	  -Wl,-rpath,/opt/rocm/lib
 
+# drag / lift and probe through the facade (no oracle: known answers)
+$(CPPFORCES): tests/cpp/test_forces.cc include/gls_operator.hpp include/gls_op.h include/gls_mesh.h \
+              $(LIBDIR)/libglsamd.so $(LIBDIR)/libglsmesh.so
+	@mkdir -p tests/cpp/build
+	$(CXX) -O2 -std=c++17 -Wall -D__HIP_PLATFORM_AMD__ -Iinclude -I/opt/rocm/include -o $@ $< \
+	  -L$(LIBDIR) -lglsamd -lglsmesh -L/opt/rocm/lib -lamdhip64 \
+	  -Wl,-rpath,'$$ORIGIN/../../../$(LIBDIR)' -Wl,-rpath,/opt/rocm/lib
+
 clean:
-	rm -f $(LIBDIR)/*.so $(CPPTEST)
+	rm -f $(LIBDIR)/*.so $(CPPTEST) $(CPPFORCES)
 	rm -rf $(OBJDIR)
 	$(MAKE) -C oracle clean
 

@@ -912,6 +912,64 @@ gls_dist_get_max_u(glsDist d, void *vec, double *u_max, void *stream)
   GLS_CATCH
 }
 
+// sum of host values[count] over the ranks, back into values; synchronises
+static void
+allreduce_host_sum(glsDist d, double *values, int64_t count, hipStream_t s)
+{
+  double *buf = nullptr;
+  HIP_THROW(hipMallocAsync((void **)&buf, (size_t)std::max<int64_t>(count, 1) * sizeof(double), s));
+  HIP_THROW(hipMemcpyAsync(buf, values, (size_t)count * sizeof(double), hipMemcpyHostToDevice, s));
+  d->tx->allreduce(d, buf, count, false, s);
+  HIP_THROW(hipMemcpyAsync(values, buf, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIP_THROW(hipFreeAsync(buf, s));
+  HIP_THROW(hipStreamSynchronize(s));
+}
+
+glsStatus
+gls_dist_surface_force(glsDist d, void *vec, double *force, void *stream)
+{
+  GLS_TRY
+  if (!d || !vec || !force)
+    throw std::runtime_error("gls_dist_surface_force: null argument");
+  // simulation.cc:445, 473-497, 509-510: update_ghost_values; the faces of
+  // the locally owned cells; Utilities::MPI::sum
+  if (gls_dist_update_ghost_values(d, vec, stream) != 0)
+    throw std::runtime_error(gls_last_error());
+  double local[3] = {0, 0, 0};
+  if (gls_op_surface_force(d->op, vec, local, stream) != 0)
+    throw std::runtime_error(gls_last_error());
+  allreduce_host_sum(d, local, d->op->dim, (hipStream_t)stream);
+  for (int c = 0; c < d->op->dim; ++c)
+    force[c] = local[c];
+  GLS_CATCH
+}
+
+glsStatus
+gls_dist_probe(glsDist d, void *vec, double *values, void *stream)
+{
+  GLS_TRY
+  if (!d || !vec || !values)
+    throw std::runtime_error("gls_dist_probe: null argument");
+  if (gls_dist_update_ghost_values(d, vec, stream) != 0)
+    throw std::runtime_error(gls_last_error());
+  // value sums and cell counts over the ranks (every rank sets the same
+  // points; a cell is processed by one rank), then the average
+  const std::vector<int64_t> &cnt = gls::probe_counts(d->op);
+  const int64_t               np = (int64_t)cnt.size(), nc = d->op->dim + 1;
+  std::vector<double>         buf((size_t)np * (nc + 1), 0.0);
+  gls::probe_run(d->op, vec, false, buf.data(), (hipStream_t)stream);
+  for (int64_t p = 0; p < np; ++p)
+    buf[(size_t)(np * nc + p)] = (double)cnt[(size_t)p];
+  allreduce_host_sum(d, buf.data(), np * (nc + 1), (hipStream_t)stream);
+  for (int64_t p = 0; p < np; ++p)
+    {
+      const double n = buf[(size_t)(np * nc + p)];
+      for (int64_t c = 0; c < nc; ++c)
+        values[p * nc + c] = n > 0 ? buf[(size_t)(p * nc + c)] / n : 0.0;
+    }
+  GLS_CATCH
+}
+
 glsStatus
 gls_dist_interior_bricks(glsDist d, int64_t *n_interior, int64_t *n_total)
 {

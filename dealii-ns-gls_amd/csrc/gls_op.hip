@@ -1706,6 +1706,7 @@ gls_op_create(const glsOpDesc *d, glsOp *out)
   op->n_dofs        = d->n_nodes * (d->dim + 1);
   op->n_owned_dofs  = d->n_owned_nodes * (d->dim + 1);
   op->basis         = Basis1D(d->degree);
+  op->own_mapping   = d->mapping_points != nullptr;
   const int dim = d->dim, n = d->degree + 1;
   op->nq            = dim == 3 ? n * n * n : n * n;
   op->nf            = 2 + 3 * dim + dim * dim;
@@ -1962,6 +1963,7 @@ gls_op_destroy(glsOp op)
     (void)hipHostFree(op->h_sweep_flag);
   op->stage.release();
   gls::faces_release(op);
+  gls::forces_release(op);
   delete op;
 }
 
@@ -1976,7 +1978,8 @@ gls_op_set_parameters(glsOp op, const glsOpParams *prm)
   if (td && prm->theta != 1.0)
     throw std::runtime_error("consider_time_derivative requires theta == 1 "
                              "(operator_ns.cc:126-129)");
-  op->prm = *prm;
+  op->prm      = *prm;
+  op->have_prm = true;
   op->version++;
   GLS_CATCH
 }

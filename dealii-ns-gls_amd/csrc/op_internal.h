@@ -60,6 +60,29 @@ struct OutflowFaces
   void               *d_ustar  = nullptr; // [n][nqf][dim] face_velocity
   void               *d_target = nullptr; // [n][nqf][dim] face_target_velocity
 };
+
+// drag / lift faces and the solution probe (forces.hip): per face the
+// internal cell, the face number and the cell's node coordinates; per probe
+// pair the internal cell and the reference point, grouped by point
+struct Forces
+{
+  bool     have_faces = false, have_points = false; // the matching set_* was called
+  int64_t  n_faces = 0;
+  int      n_q_1d  = 3;
+  int64_t *d_cell   = nullptr; // [n_faces] internal cell
+  int32_t *d_face   = nullptr; // [n_faces] 2 * axis + side
+  double  *d_coords = nullptr; // [n_faces][(k+1)^dim][dim]
+  double  *d_out    = nullptr; // [n_faces][dim] per-face forces
+  double  *h_total  = nullptr; // [3] their sum, host-mapped; d_total: its device address
+  double  *d_total  = nullptr;
+  int64_t  n_points = 0, n_pairs = 0;
+  std::vector<int64_t> h_count;  // [n_points] cells found
+  int64_t *d_poff  = nullptr;    // [n_points + 1]
+  int64_t *d_pcell = nullptr;    // [n_pairs] internal cell
+  double  *d_pxi   = nullptr;    // [n_pairs][dim]
+  double  *h_pval  = nullptr;    // [n_points][dim + 1], host-mapped; d_pval: its device address
+  double  *d_pval  = nullptr;
+};
 } // namespace gls
 
 struct glsOp_
@@ -77,6 +100,8 @@ struct glsOp_
 
   glsOpParams prm{};
   bool        have_lin = false, have_prev = false, have_old_grad = false;
+  bool        have_prm = false;    // gls_op_set_parameters was called (nu)
+  bool        own_mapping = false; // created with glsOpDesc::mapping_points
   // bumped by every call that changes what a launch captures by value
   // (parameters, table producers): a captured V-cycle graph of the
   // multigrid (csrc/mg.hip) is re-captured when a level's version moved
@@ -108,6 +133,7 @@ struct glsOp_
   int       device     = 0;
   gls::VecStage stage; // caller vector layout (host memory / dof permutation)
   gls::OutflowFaces faces; // weak outflow boundary faces (faces.hip)
+  gls::Forces forces;      // drag / lift faces and probe points (forces.hip)
   // gls_gmres_solve workspace (Krylov basis and vectors), grown on demand
   void     *gmres_ws       = nullptr;
   size_t    gmres_ws_bytes = 0;
@@ -283,6 +309,13 @@ void faces_linearization(const glsOp_ *op, const void *lin, hipStream_t s);
 void faces_apply(const glsOp_ *op, bool residual, void *dst, const void *src, hipStream_t s);
 void faces_diagonal(const glsOp_ *op, void *diag, bool f64_out, hipStream_t s);
 void faces_element_matrices(const glsOp_ *op, void *emat, int64_t b, int64_t e, hipStream_t s);
+// surface force and probe lists (forces.hip)
+void forces_release(glsOp_ *op);
+// the probe values of the local cells into host values[n_points][dim + 1],
+// averaged over the cells found (avg) or their plain sums (the partitioned
+// probe reduces sums and counts); returns synchronised
+void probe_run(glsOp_ *op, const void *vec, bool avg, double *values, hipStream_t s);
+const std::vector<int64_t> &probe_counts(const glsOp_ *op);
 // the brick vmult with the smoother step fused into its write-out needs the
 // whole A x inside the kernel: single domain, no face terms
 inline bool

@@ -49,6 +49,8 @@ EXPORTS = [
     "gls_dist_gmres_solve", "gls_op_element_matrices",
     "gls_op_system_matrix", "gls_op_n_outflow_faces", "gls_op_outflow_face_points",
     "gls_op_set_outflow_target",
+    "gls_op_set_force_faces", "gls_op_surface_force", "gls_op_surface_force_faces",
+    "gls_op_set_probe_points", "gls_op_probe", "gls_dist_surface_force", "gls_dist_probe",
 ]
 
 GLS_MEM_DEVICE, GLS_MEM_HOST = 0, 1
@@ -189,6 +191,13 @@ def lib():
         L.gls_op_n_outflow_faces.argtypes = [vp, C.POINTER(i64), C.POINTER(C.c_int)]
         L.gls_op_outflow_face_points.argtypes = [vp, vp]
         L.gls_op_set_outflow_target.argtypes = [vp, vp, vp]
+        L.gls_op_set_force_faces.argtypes = [vp, i64, vp, vp, vp, C.c_int]
+        L.gls_op_surface_force.argtypes = [vp, vp, vp, vp]
+        L.gls_op_surface_force_faces.argtypes = [vp, vp, vp, vp]
+        L.gls_op_set_probe_points.argtypes = [vp, i64, vp, vp, vp]
+        L.gls_op_probe.argtypes = [vp, vp, vp, vp]
+        L.gls_dist_surface_force.argtypes = [vp, vp, vp, vp]
+        L.gls_dist_probe.argtypes = [vp, vp, vp, vp]
         L.gls_mg_coarse_statistics.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.gls_mg_coarse_setup_times.argtypes = [vp, vp, C.POINTER(C.c_int)]
         L.gls_amg_create.argtypes = [i64, vp, vp, vp, C.POINTER(AMGParams), C.POINTER(vp)]
@@ -616,6 +625,51 @@ class NavierStokesOperator:
         _check(lib().gls_op_get_max_u(self.h, _vptr(vec), C.byref(out), _stream()))
         return out.value
 
+    # --- SimulationCylinder::postprocess (simulation.cc:433-549)
+    def set_force_faces(self, cells, face_no, n_q_1d=3):
+        """The boundary faces of surface_force as (cells, face_no) (what
+        glsmesh.boundary_faces returns; cells index this operator's cell
+        list), QGauss(n_q_1d) per face direction (reference: 3); the geometry
+        is the mesh's the operator was built on."""
+        fc = np.ascontiguousarray(cells, dtype=np.int64)
+        fn = np.ascontiguousarray(face_no, dtype=np.int32)
+        if fc.shape != fn.shape or fc.ndim != 1:
+            raise GlsError("set_force_faces: cells and face_no must be 1D and of one length")
+        _check(lib().gls_op_set_force_faces(self.h, len(fc), fc.ctypes.data, fn.ctypes.data,
+                                            self._keep[1].ctypes.data, int(n_q_1d)))
+        self.n_force_faces = len(fc)
+
+    def surface_force(self, vec):
+        """Sum over the force faces of (-p I + 2 nu eps(u)) . n JxW, n the
+        normal pointing into the cell (simulation.cc:487-495): ndarray [dim]."""
+        out = np.zeros(self.dim)
+        _check(lib().gls_op_surface_force(self.h, _vptr(vec), out.ctypes.data, _stream()))
+        return out
+
+    def surface_force_faces(self, vec):
+        """The same per face, [n_faces][dim], in the order of set_force_faces."""
+        out = np.zeros((getattr(self, "n_force_faces", 0), self.dim))
+        _check(lib().gls_op_surface_force_faces(self.h, _vptr(vec), out.ctypes.data, _stream()))
+        return out
+
+    def set_probe_points(self, xyz):
+        """Points [n_points][dim] of probe(); returns the number of cells
+        found per point (0: the point is in no cell of this operator)."""
+        x = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, self.dim)
+        found = np.zeros(len(x), dtype=np.int64)
+        _check(lib().gls_op_set_probe_points(self.h, len(x), x.ctypes.data,
+                                             self._keep[1].ctypes.data, found.ctypes.data))
+        self.n_probe_points = len(x)
+        return found
+
+    def probe(self, vec):
+        """All dim+1 components at the probe points, averaged over the cells
+        that contain a point (point_values<1>(avg), simulation.cc:537-538):
+        ndarray [n_points][dim+1]."""
+        out = np.zeros((getattr(self, "n_probe_points", 0), self.dim + 1))
+        _check(lib().gls_op_probe(self.h, _vptr(vec), out.ctypes.data, _stream()))
+        return out
+
     def set_vector_layout(self, memory="device", dof_map=None):
         """Caller vector layout (gls_op_set_vector_layout): memory "host"
         (numpy arrays, staged) or "device" (torch tensors); dof_map[i] = the
@@ -712,6 +766,21 @@ class PartitionedOperator:
         out = C.c_double()
         _check(lib().gls_dist_get_max_u(self.h, _ptr(vec), C.byref(out), _stream()))
         return out.value
+
+    def surface_force(self, vec):
+        """surface_force of the partitioned operator: ghost import, the
+        rank's own faces (op.set_force_faces), all-reduce sum
+        (simulation.cc:509-510)."""
+        out = np.zeros(self.op.dim)
+        _check(lib().gls_dist_surface_force(self.h, _ptr(vec), out.ctypes.data, _stream()))
+        return out
+
+    def probe(self, vec):
+        """probe of the partitioned operator (every rank sets the same
+        points): value sums and cell counts all-reduced, then divided."""
+        out = np.zeros((getattr(self.op, "n_probe_points", 0), self.op.dim + 1))
+        _check(lib().gls_dist_probe(self.h, _ptr(vec), out.ctypes.data, _stream()))
+        return out
 
     def interior_bricks(self):
         a, b = C.c_int64(), C.c_int64()

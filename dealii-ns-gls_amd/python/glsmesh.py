@@ -275,6 +275,13 @@ def boundary_faces(mesh, bid):
     return cells[order], faces[order]
 
 
+def _mesh_params(mesh):
+    """The generator parameters of a mesh or of a view of one (ShuffledMesh)."""
+    while not hasattr(mesh, "params") and hasattr(mesh, "base"):
+        mesh = mesh.base
+    return mesh.params
+
+
 # --------------------------------------------------------------------- decks
 # the five input decks of the reference (input/*.json), shipped as package data
 DECK_DIR = os.path.normpath(os.path.join(_HERE, "..", "data", "decks"))
@@ -335,6 +342,33 @@ class Deck:
         if self.simulation != "cylinder" or self.outflow not in ("cut", "nitsche"):
             return None
         return boundary_faces(mesh, 1)
+
+    # --- SimulationCylinder::postprocess (simulation.cc:433-549)
+    def cylinder_faces(self, mesh):
+        """(cells, face_no) of the cylinder's boundary faces (boundary id 2,
+        simulation.cc:478-480): the faces of the drag / lift integral."""
+        return boundary_faces(mesh, 2)
+
+    def force_scaling(self, mesh):
+        """Force -> coefficient: 2 / (D u_bar^2), divided by H in 3D, with
+        u_bar = u_max * 2/3 (2D) or 4/9 (3D) when the walls are no-slip
+        (simulation.cc:500-507); D and H are the mesh's."""
+        prm = _mesh_params(mesh)
+        u_bar = self.u_max
+        if self.no_slip_wall:
+            u_bar *= 2.0 / 3.0 if mesh.dim == 2 else 4.0 / 9.0
+        scaling = 2.0 / prm["diameter"] / u_bar ** 2
+        if mesh.dim == 3:
+            scaling /= prm["height"]
+        return scaling
+
+    def pressure_probe_points(self, mesh):
+        """The two points of the pressure difference, (-D/2, 0[, 0]) (front)
+        and (+D/2, 0[, 0]) (back), simulation.cc:517-520."""
+        pts = np.zeros((2, mesh.dim))
+        pts[0, 0] = -_mesh_params(mesh)["diameter"] / 2.0
+        pts[1, 0] = +_mesh_params(mesh)["diameter"] / 2.0
+        return pts
 
     def inflow_velocity(self, points, t=0.0, height=0.41):
         """InflowBoundaryValues::Channel (simulation.cc:25-76, built at

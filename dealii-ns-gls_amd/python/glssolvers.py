@@ -182,3 +182,51 @@ def wire_newton(solver, op, cmask, linear_solver, preconditioner=None):
     solver.evaluate_residual = evaluate_residual
     solver.solve_with_jacobian = solve_with_jacobian
     return solver
+
+
+class CylinderPostprocess:
+    """SimulationCylinder::postprocess (simulation.cc:433-549): the drag and
+    lift coefficients of the cylinder and the pressure difference across it,
+    evaluated on the device (NavierStokesOperator.surface_force / probe, or a
+    PartitionedOperator's), one line `t\\tc_D\\tc_L\\tdp\\n` appended to `path`
+    per call and flushed (simulation.cc:546-548).
+
+    op: the operator (its viscosity set), deck / mesh: the deck and the mesh
+    the operator was built on.  Called by the user after a time step,
+    `c_d, c_l, dp = post(t, solution)`, or assigned to
+    NonLinearSolverBase.postprocess, which passes the solution only: the time
+    written is then the attribute `t`, which the time loop keeps current."""
+
+    def __init__(self, op, deck, mesh, path=None):
+        self.op = op
+        self.scaling = deck.force_scaling(mesh)
+        cells, face_no = deck.cylinder_faces(mesh)
+        op.set_force_faces(cells, face_no, 3)
+        self.n_found = op.set_probe_points(deck.pressure_probe_points(mesh))
+        self.dim = mesh.dim
+        self.t = 0.0
+        self.path = path
+        self._file = open(path, "a") if path is not None else None
+
+    def __call__(self, t, solution=None):
+        if solution is None:  # NonLinearSolverBase.postprocess(solution)
+            t, solution = self.t, t
+        force = np.asarray(self.op.surface_force(solution), dtype=np.float64)
+        values = np.asarray(self.op.probe(solution), dtype=np.float64)
+        c_d, c_l = float(force[0] * self.scaling), float(force[1] * self.scaling)
+        dp = float(values[0, self.dim] - values[1, self.dim])
+        if self._file is not None:
+            self._file.write(f"{t:g}\t{c_d:g}\t{c_l:g}\t{dp:g}\n")
+            self._file.flush()
+        return c_d, c_l, dp
+
+    def close(self):
+        if self._file is not None:
+            self._file.close()
+            self._file = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

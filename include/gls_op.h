@@ -44,6 +44,10 @@
  *   gls_op_compute_inverse_diagonal  OperatorBase::compute_inverse_diagonal
  *                                      operator_base.h:26-27, operator_ns.cc:195-225
  *   gls_op_m                         OperatorBase::m  operator_base.h:20-21
+ *   gls_op_surface_force /
+ *   gls_op_probe                     SimulationCylinder::postprocess
+ *                                      simulation.cc:433-549 (drag / lift
+ *                                      face integral, pressure point values)
  *   gls_op_upload_tables /
  *   gls_op_download_tables           host-produced / inspected per-q tables
  *                                      (u_star_value ... operator_ns.h:120-132)
@@ -202,8 +206,8 @@ int       gls_op_precision(glsOp op);
 /* Caller-side vector layout of every vector argument of the gls_op_* calls
  * below that take whole dof vectors (set_linearization_point,
  * set_previous_solution, vmult, evaluate_residual(_plain), evaluate_rhs,
- * set_constraint_values, compute_inverse_diagonal, get_max_u, and x / b of
- * gls_gmres_solve):
+ * set_constraint_values, compute_inverse_diagonal, get_max_u, surface_force,
+ * probe, and x / b of gls_gmres_solve):
  *   memory   GLS_MEM_DEVICE (default) or GLS_MEM_HOST: host pointers, as the
  *            reference's LinearAlgebra::distributed::Vector<Number> in host
  *            memory (config.h:9-10); staged through device buffers, the
@@ -275,6 +279,39 @@ glsStatus gls_op_compute_inverse_diagonal(glsOp op, void *inv_diag,
  * (main.cc:913-920).  Partitioned operators: gls_dist_get_max_u adds the
  * MPI max. */
 glsStatus gls_op_get_max_u(glsOp op, const void *vec, double *u_max, void *stream);
+
+/* Drag / lift: SimulationCylinder::postprocess, simulation.cc:447-511.  The
+ * force on a list of boundary faces ((caller cell, face number 2*axis + side)
+ * as glsOpDesc.outflow_*),
+ *   F = sum_faces sum_q (-p I + 2 nu eps(u)) . n JxW,
+ * n = -(outward unit normal of the cell) (:489-494), nu from
+ * gls_op_set_parameters, `vec` read plain (no constraints), QGauss(n_q_1d)
+ * per face direction (first tangential axis fastest; the reference takes 3
+ * for every degree, :451), geometry from the cells' node_coords
+ * (host [n_nodes][dim], the array glsOpDesc.node_coords held; copied).
+ * Per-face forces come in the caller's face order; their sum is taken in
+ * that order by one workgroup, so the result is bitwise repeatable and does
+ * not depend on the operator's internal cell order.  Calling set again
+ * replaces the list, n_faces = 0 leaves an empty list (force 0).  Errors: bad
+ * cell or face number, an operator created with mapping_points, a force
+ * call before set_force_faces or before gls_op_set_parameters.  `vec`
+ * honours gls_op_set_vector_layout; the calls return synchronised. */
+glsStatus gls_op_set_force_faces(glsOp op, int64_t n_faces, const int64_t *cells,
+                                 const int32_t *face_no, const double *node_coords /* host [n_nodes][dim] */,
+                                 int n_q_1d /* 1..4, reference: 3 */);
+glsStatus gls_op_surface_force(glsOp op, const void *vec, double *force /* host [dim] */, void *stream);
+glsStatus gls_op_surface_force_faces(glsOp op, const void *vec, double *per_face /* host [n_faces][dim] */, void *stream);
+/* Point probe: RemotePointEvaluation + VectorTools::point_values<1>(avg),
+ * simulation.cc:512-541.  set_probe_points finds, for each point
+ * (xyz host [n_points][dim]), every local cell whose Q_k mapping contains it
+ * (Newton inversion from the cells of the closest node, reference-coordinate
+ * tolerance 1e-6, clamped to the unit cell) and reports the number of cells
+ * per point (n_cells_found, may be NULL); gls_op_probe evaluates all dim+1
+ * components of `vec` at every (cell, point) pair and averages per point into
+ * values (host [n_points][dim+1]); a point in no cell gives 0. */
+glsStatus gls_op_set_probe_points(glsOp op, int64_t n_points, const double *xyz, const double *node_coords,
+                                  int64_t *n_cells_found /* host [n_points] */);
+glsStatus gls_op_probe(glsOp op, const void *vec, double *values /* host [n_points][dim+1] */, void *stream);
 /* the pieces of compute_inverse_diagonal for a partitioned operator: the
  * rank-local assembled diagonal (constrained owned components 1), then —
  * after the caller's compress(add) of the ghost partials (gls_dist_compress_
@@ -491,6 +528,14 @@ glsStatus gls_dist_compress_add(glsDist d, void *vec, void *stream);
 /* get_max_u of the partitioned operator (operator_ns.cc:530-568): ghost
  * import, local max (gls_op_get_max_u), RCCL all-reduce max */
 glsStatus gls_dist_get_max_u(glsDist d, void *vec, double *u_max, void *stream);
+/* gls_op_surface_force / gls_op_probe of the partitioned operator
+ * (Utilities::MPI::sum, simulation.cc:509-510): ghost import, the local
+ * call on the rank's own list (faces and points belong to the rank that
+ * holds the cell; every rank sets the same points, a rank without faces an
+ * empty list), all-reduce sum; the probe reduces the value sums and the
+ * cell counts, then divides.  Rank calls as gls_dist_get_max_u. */
+glsStatus gls_dist_surface_force(glsDist d, void *vec, double *force, void *stream);
+glsStatus gls_dist_probe(glsDist d, void *vec, double *values, void *stream);
 
 /* ---- device-resident Krylov solver:
  * LinearSolverGMRES::solve, solver_l.cc:45-74 — deal.II SolverGMRES with

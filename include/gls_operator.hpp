@@ -20,6 +20,7 @@
 #include "gls_op.h"
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <functional>
 #include <stdexcept>
@@ -102,7 +103,12 @@ public:
   }
   Operator(const Operator &)            = delete;
   Operator &operator=(const Operator &) = delete;
-  Operator(Operator &&o) noexcept : h(std::exchange(o.h, nullptr)) {}
+  Operator(Operator &&o) noexcept
+    : h(std::exchange(o.h, nullptr))
+    , n_force_faces(o.n_force_faces)
+    , n_probe_points(o.n_probe_points)
+    , n_dim(o.n_dim)
+  {}
   Operator &
   operator=(Operator &&o) noexcept
   {
@@ -110,7 +116,10 @@ public:
       {
         if (h)
           gls_op_destroy(h);
-        h = std::exchange(o.h, nullptr);
+        h              = std::exchange(o.h, nullptr);
+        n_force_faces  = o.n_force_faces;
+        n_probe_points = o.n_probe_points;
+        n_dim          = o.n_dim;
       }
     return *this;
   }
@@ -205,6 +214,65 @@ public:
     return u;
   }
 
+  // SimulationCylinder::postprocess (simulation.cc:447-511): the faces of
+  // the drag / lift integral as (caller cell, face number 2*axis + side),
+  // node_coords [n_nodes][dim] the array the descriptor held, QGauss(n_q_1d)
+  // per face direction (reference: 3)
+  void
+  set_force_faces(const std::vector<int64_t> &cells, const std::vector<int32_t> &face_no,
+                  const double *node_coords, int n_q_1d = 3)
+  {
+    if (cells.size() != face_no.size())
+      throw Error("set_force_faces: cells and face_no differ in length");
+    check(gls_op_set_force_faces(h, (int64_t)cells.size(), cells.data(), face_no.data(),
+                                 node_coords, n_q_1d),
+          "set_force_faces");
+    n_force_faces = (int64_t)cells.size();
+  }
+
+  // sum over the faces of (-p I + 2 nu eps(u)) . n JxW, n pointing into the
+  // cell (simulation.cc:487-495): components 0 .. dim-1 (the rest 0)
+  std::array<double, 3>
+  surface_force(const void *src, void *stream = nullptr) const
+  {
+    std::array<double, 3> f{{0.0, 0.0, 0.0}};
+    check(gls_op_surface_force(h, src, f.data(), stream), "surface_force");
+    return f;
+  }
+
+  // the same per face, [n_faces][dim] in the order of set_force_faces
+  std::vector<double>
+  surface_force_faces(int dim, const void *src, void *stream = nullptr) const
+  {
+    std::vector<double> f((size_t)(n_force_faces * dim), 0.0);
+    check(gls_op_surface_force_faces(h, src, f.data(), stream), "surface_force_faces");
+    return f;
+  }
+
+  // simulation.cc:512-541: the probe points [n_points][dim]; returns the
+  // number of cells found per point
+  std::vector<int64_t>
+  set_probe_points(int dim, const std::vector<double> &xyz, const double *node_coords)
+  {
+    std::vector<int64_t> found(xyz.size() / (size_t)dim, 0);
+    check(gls_op_set_probe_points(h, (int64_t)found.size(), xyz.data(), node_coords,
+                                  found.data()),
+          "set_probe_points");
+    n_probe_points = (int64_t)found.size();
+    n_dim          = dim;
+    return found;
+  }
+
+  // all dim+1 components at the probe points, averaged over the cells found:
+  // [n_points][dim+1]
+  std::vector<double>
+  probe(const void *src, void *stream = nullptr) const
+  {
+    std::vector<double> v((size_t)(n_probe_points * (n_dim + 1)), 0.0);
+    check(gls_op_probe(h, src, v.data(), stream), "probe");
+    return v;
+  }
+
   // identity rows after a ghost export-add (distributed vmult)
   void
   apply_identity_rows(void *dst, const void *src, void *stream = nullptr) const
@@ -257,7 +325,9 @@ public:
   }
 
 private:
-  glsOp h = nullptr;
+  glsOp   h = nullptr;
+  int64_t n_force_faces = 0, n_probe_points = 0; // sizes of the lists set above
+  int     n_dim = 0;
 };
 
 // PreconditionerGMG: level operators (MGNumber precision), transfers,
