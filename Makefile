@@ -15,7 +15,8 @@ CXXFLAGS := -O3 -std=c++17 -fPIC -Wall -Wextra -Wno-unused-parameter
 HIPFLAGS := -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -munsafe-fp-atomics \
             -Wall -Wno-unused-parameter -Wno-unused-function
 
-# rocsolver/rocblas: dense LU of the coarse multigrid level only; rccl: ghost exchange
+# rocsolver/rocblas: the direct solvers of the coarse multigrid level only (dense LU,
+# the nested-dissection fronts); rccl: ghost exchange
 # rocprofiler-sdk-roctx: the timer sections' roctx ranges (trace.cc)
 AMD_LIBS := -L/opt/rocm/lib -lrocsolver -lrocblas -lrccl -lrocprofiler-sdk-roctx -Wl,-rpath,/opt/rocm/lib
 

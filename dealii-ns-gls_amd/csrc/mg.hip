@@ -17,6 +17,7 @@
 #include "kernels.h"
 #include "op_internal.h"
 #include "cgs.h"
+#include "coarse_nd_solver.h"
 #include "trace.h"
 
 #include <chrono>
@@ -28,6 +29,7 @@
 #include <algorithm>
 #include <type_traits>
 #include <cmath>
+#include <functional>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -665,6 +667,14 @@ struct glsMG_
   // last dense-coarse setup: assembly / getrf / getri wall ms, cell colours
   double         coarse_setup_ms[3] = {0, 0, 0};
   int            coarse_colors      = 0;
+  // the nested-dissection form of the direct solver (gls_mg_set_coarse_direct,
+  // coarse_nd.hip): it replaces the dense block, its inverse and the GEMV
+  // between the condensed right-hand side and the interior back-substitution;
+  // nd_failed: a pivot block was singular, the dense solver took over
+  int            coarse_method = GLS_COARSE_DENSE, nd_leaf_cells = 0;
+  bool           nd_failed     = false;
+  gls::NdSolver *nd            = nullptr;
+  double         nd_plan_ms    = 0;
   // coarse GMRES (coarse_iterate): FP64 Krylov workspace, two level-
   // precision operand buffers, statistics of the last solve
   // finest-level FP64 defect for the fused copy_to_mg (mg_vcycle_device; null:
@@ -1230,6 +1240,9 @@ k_narrow(float *__restrict__ out, const double *__restrict__ in, int64_t n, int6
 // pivoting, FP64), F = E_BI C, G = C E_IB, and the element Schur complement
 // S = E_BB - F E_IB (column major [c][b2][b1]), assembled like E.
 constexpr int COND_MAXI = 32;
+// cells per leaf of the nested-dissection tree where the caller gives none
+// (the fastest V-cycle of the leaf-size sweep at Re3900 r0)
+constexpr int ND_DEFAULT_LEAF_CELLS = 50;
 template <typename T>
 __global__ void __launch_bounds__(256)
   k_condense(const T *__restrict__ E, int ndof, const int32_t *__restrict__ lint, int ni,
@@ -1435,9 +1448,13 @@ k_scatter_emat(double *__restrict__ A, int64_t nf, const T *__restrict__ E,
 // the Trilinos matrix, multigrid.cc:448-455): one element-matrix launch over
 // all coarse cells, then one scatter launch per cell colour (greedy colouring
 // on the host, cells of a colour share no node), summed in FP64
+// With `fronts` the cell blocks go to that function (the nested-dissection
+// solver's fronts) instead of the dense block.
+using CellBlockSink = std::function<void(gls::NdCellBlocks &)>;
 template <typename T>
 bool
-assemble_free_block(glsMG_ *mg, const std::vector<int32_t> &freel, hipStream_t s)
+assemble_free_block(glsMG_ *mg, const std::vector<int32_t> &freel, hipStream_t s,
+                    const CellBlockSink &fronts = nullptr)
 {
   bool ok = true; // false: a condensed cell's interior block is singular
   glsOp         op   = mg->ops[0];
@@ -1496,8 +1513,20 @@ assemble_free_block(glsMG_ *mg, const std::vector<int32_t> &freel, hipStream_t s
   HIP_THROW(hipMemcpyAsync(d_order, order.data(), order.size() * sizeof(int32_t),
                            hipMemcpyHostToDevice, s));
   gls::op_element_matrices_device(op, E, 0, nc_, s);
-  HIP_THROW(hipMemsetAsync(mg->d_lu, 0, (size_t)nf * nf * sizeof(double), s));
-  if (!mg->cond)
+  gls::NdCellBlocks cb{};
+  cb.cell_caller   = op->cell_perm.empty() ? nullptr : op->cell_perm.data();
+  cb.d_color_cells = (const int32_t *)d_order;
+  cb.color_begin   = cbeg.data();
+  cb.n_colors      = n_colors;
+  if (!fronts)
+    HIP_THROW(hipMemsetAsync(mg->d_lu, 0, (size_t)nf * nf * sizeof(double), s));
+  if (!mg->cond && fronts)
+    {
+      cb.blocks = E, cb.f64 = std::is_same<T, double>::value, cb.nloc = ndof;
+      cb.cell_dof = cdof.data();
+      fronts(cb);
+    }
+  else if (!mg->cond)
     {
       const int64_t per = (int64_t)ndof * ndof;
       for (int k = 0; k < n_colors; ++k)
@@ -1567,7 +1596,12 @@ assemble_free_block(glsMG_ *mg, const std::vector<int32_t> &freel, hipStream_t s
       for (int32_t b : hbad)
         ok = ok && b == 0;
       const int64_t per = (int64_t)nb * nb;
-      for (int k = 0; k < n_colors; ++k)
+      if (fronts && ok)
+        {
+          cb.blocks = Sd, cb.f64 = true, cb.nloc = nb, cb.cell_dof = cdb.data();
+          fronts(cb);
+        }
+      for (int k = 0; k < n_colors && !fronts; ++k)
         {
           const int64_t cnt = cbeg[(size_t)k + 1] - cbeg[(size_t)k];
           hipLaunchKernelGGL(k_scatter_emat<double>, g1(cnt * per), dim3(256), 0, s, mg->d_lu, nf,
@@ -1615,7 +1649,10 @@ coarse_lu_setup_t(glsMG_ *mg, hipStream_t s)
   glsOp         op = mg->ops[0];
   const int64_t n  = op->n_dofs;
   const int     nc = op->dim + 1;
-  if (n > 40000)
+  // (the nested-dissection solver checks the free device memory instead)
+  const bool nd = mg->coarse_method == GLS_COARSE_ND && !mg->nd_failed &&
+                  !coarse_reference("columns");
+  if (n > 40000 && !nd)
     throw std::runtime_error("dense LU coarse solver: coarse level too large");
   std::vector<int32_t> freel;
   freel.reserve((size_t)n);
@@ -1677,11 +1714,6 @@ coarse_lu_setup_t(glsMG_ *mg, hipStream_t s)
   check_blas(rocblas_set_stream(mg->blas, s), "rocblas_set_stream");
   if (mg->d_free && mg->n_free != nf)
     throw std::runtime_error("dense LU coarse solver: constrained dofs changed");
-  // the FP64 factors are released after an FP32 setup (k_narrow below)
-  if (!mg->d_lu)
-    HIP_THROW(hipMalloc((void **)&mg->d_lu, (size_t)nf * nf * sizeof(double)));
-  if (!mg->d_ipiv)
-    HIP_THROW(hipMalloc((void **)&mg->d_ipiv, (size_t)nf * sizeof(rocblas_int)));
   if (!mg->d_free)
     {
       HIP_THROW(hipMalloc((void **)&mg->d_info, sizeof(rocblas_int)));
@@ -1696,6 +1728,115 @@ coarse_lu_setup_t(glsMG_ *mg, hipStream_t s)
     throw std::runtime_error("dense LU coarse solver: constrained dofs changed");
   HIP_THROW(hipMemcpyAsync(mg->d_free, freel.data(), (size_t)nf * sizeof(int32_t),
                            hipMemcpyHostToDevice, s));
+  // a cell's interior block E_II is singular: start over without the
+  // static condensation (the free-dof buffers are sized for nf, the
+  // nested-dissection plan for the condensed dofs)
+  auto restart_without_condensation = [&]() {
+    HIP_THROW(hipStreamSynchronize(s));
+    for (void **q : {(void **)&mg->d_lu, (void **)&mg->d_ipiv, (void **)&mg->d_info,
+                     (void **)&mg->d_rhs, (void **)&mg->d_free, (void **)&mg->d_free_in})
+      {
+        HIP_THROW(hipFree(*q));
+        *q = nullptr;
+      }
+    gls::nd_solver_destroy(mg->nd);
+    mg->nd          = nullptr;
+    mg->n_free      = 0;
+    mg->cond        = false;
+    mg->cond_failed = true;
+    fprintf(stderr, "[glsamd] coarse solver: singular interior block in a coarse cell, "
+                    "assembling without static condensation\n");
+  };
+  // per GEMV column i: the (cell, boundary slot) pairs of dof fin[i]
+  // (k_cond_rhs)
+  auto cond_tables = [&](const std::vector<int32_t> &fin) {
+    const int     nb = mg->cond_nb, nq = op->nq;
+    std::vector<std::vector<int32_t>> at((size_t)n);
+    for (int64_t c = 0; c < op->n_cells; ++c)
+      {
+        const uint32_t *cn = &op->h_cell_nodes[(size_t)gls::ext_cell(op, c) * nq];
+        for (int b = 0; b < nb; ++b)
+          {
+            const int     l = mg->cond_lbnd[(size_t)b];
+            const int64_t d = (int64_t)cn[l / nc] * nc + l % nc;
+            if (!((op->h_cmask[(size_t)cn[l / nc]] >> (l % nc)) & 1))
+              at[(size_t)d].push_back((int32_t)(c * nb + b));
+          }
+      }
+    std::vector<int32_t> off(1, 0), ent;
+    for (int64_t i = 0; i < nf; ++i)
+      {
+        for (int32_t e : at[(size_t)fin[(size_t)i]])
+          ent.push_back(e);
+        off.push_back((int32_t)ent.size());
+      }
+    for (int32_t **q : {&mg->d_rg_off, &mg->d_rg_ent})
+      if (*q)
+        {
+          HIP_THROW(hipStreamSynchronize(s));
+          HIP_THROW(hipFree(*q));
+          *q = nullptr;
+        }
+    HIP_THROW(hipMalloc((void **)&mg->d_rg_off, off.size() * 4));
+    HIP_THROW(hipMalloc((void **)&mg->d_rg_ent, std::max<size_t>(1, ent.size()) * 4));
+    HIP_THROW(hipMemcpy(mg->d_rg_off, off.data(), off.size() * 4, hipMemcpyHostToDevice));
+    if (!ent.empty())
+      HIP_THROW(hipMemcpy(mg->d_rg_ent, ent.data(), ent.size() * 4, hipMemcpyHostToDevice));
+  };
+  const char *e32 = getenv("GLS_COARSE_INV_F32");
+  mg->inv_f32     = !(e32 && e32[0] == '0') && mg->prec == GLS_F32;
+  if (nd)
+    {
+      // the nested-dissection solver (coarse_nd.hip): the plan once per
+      // multigrid object (the mesh and the constraints do not change), the
+      // fronts from the same cell blocks as the dense block
+      const auto w0  = std::chrono::steady_clock::now();
+      mg->nd_plan_ms = 0;
+      if (!mg->nd)
+        {
+          std::vector<int32_t> node_dofs((size_t)op->n_nodes, 0);
+          for (int32_t d : freel)
+            ++node_dofs[(size_t)(d / nc)];
+          mg->nd = gls::nd_solver_create(gls::nd_make_plan(
+            op->h_cell_nodes.data(), op->n_cells, op->nq, op->n_nodes, node_dofs.data(),
+            mg->nd_leaf_cells > 0 ? mg->nd_leaf_cells : ND_DEFAULT_LEAF_CELLS));
+          mg->nd_plan_ms = std::chrono::duration<double, std::milli>(
+                             std::chrono::steady_clock::now() - w0)
+                             .count();
+        }
+      bool factored = false;
+      if (!assemble_free_block<T>(mg, freel, s, [&](gls::NdCellBlocks &cb) {
+            factored = gls::nd_solver_factor(mg->nd, mg->blas, cb, mg->inv_f32, s);
+          }))
+        {
+          restart_without_condensation();
+          return coarse_lu_setup_t<T>(mg, s);
+        }
+      if (factored)
+        {
+          HIP_THROW(hipMemcpyAsync(mg->d_free_in, freel.data(), (size_t)nf * sizeof(int32_t),
+                                   hipMemcpyHostToDevice, s));
+          if (mg->cond)
+            cond_tables(freel);
+          HIP_THROW(hipStreamSynchronize(s));
+          return;
+        }
+      // pivoting is confined to the pivot blocks: a singular one hands the
+      // coarse level to the dense solver for good
+      HIP_THROW(hipStreamSynchronize(s));
+      gls::nd_solver_destroy(mg->nd);
+      mg->nd        = nullptr;
+      mg->nd_failed = true;
+      fprintf(stderr, "[glsamd] coarse solver: singular pivot block in the nested-dissection "
+                      "factorisation, falling back to the dense solver\n");
+      if (n > 40000)
+        throw std::runtime_error("dense LU coarse solver: coarse level too large");
+    }
+  // the FP64 factors are released after an FP32 setup (k_narrow below)
+  if (!mg->d_lu)
+    HIP_THROW(hipMalloc((void **)&mg->d_lu, (size_t)nf * nf * sizeof(double)));
+  if (!mg->d_ipiv)
+    HIP_THROW(hipMalloc((void **)&mg->d_ipiv, (size_t)nf * sizeof(rocblas_int)));
   const auto  t0 = std::chrono::steady_clock::now();
   if (columns)
     {
@@ -1717,20 +1858,7 @@ coarse_lu_setup_t(glsMG_ *mg, hipStream_t s)
     }
   else if (!assemble_free_block<T>(mg, freel, s))
     {
-      // a cell's interior block E_II is singular: start over without the
-      // static condensation (the free-dof buffers are sized for nf)
-      HIP_THROW(hipStreamSynchronize(s));
-      for (void **q : {(void **)&mg->d_lu, (void **)&mg->d_ipiv, (void **)&mg->d_info,
-                       (void **)&mg->d_rhs, (void **)&mg->d_free, (void **)&mg->d_free_in})
-        {
-          HIP_THROW(hipFree(*q));
-          *q = nullptr;
-        }
-      mg->n_free      = 0;
-      mg->cond        = false;
-      mg->cond_failed = true;
-      fprintf(stderr, "[glsamd] coarse solver: singular interior block in a coarse cell, "
-                      "assembling without static condensation\n");
+      restart_without_condensation();
       return coarse_lu_setup_t<T>(mg, s);
     }
   HIP_THROW(hipStreamSynchronize(s));
@@ -1833,41 +1961,7 @@ coarse_lu_setup_t(glsMG_ *mg, hipStream_t s)
   HIP_THROW(hipMemcpyAsync(mg->d_free_in, fin.data(), (size_t)nf * sizeof(int32_t),
                            hipMemcpyHostToDevice, s));
   if (mg->cond)
-    {
-      // per GEMV column i: the (cell, boundary slot) pairs of dof fin[i]
-      const int     nb = mg->cond_nb, nq = op->nq;
-      std::vector<std::vector<int32_t>> at((size_t)n);
-      for (int64_t c = 0; c < op->n_cells; ++c)
-        {
-          const uint32_t *cn = &op->h_cell_nodes[(size_t)gls::ext_cell(op, c) * nq];
-          for (int b = 0; b < nb; ++b)
-            {
-              const int     l = mg->cond_lbnd[(size_t)b];
-              const int64_t d = (int64_t)cn[l / nc] * nc + l % nc;
-              if (!((op->h_cmask[(size_t)cn[l / nc]] >> (l % nc)) & 1))
-                at[(size_t)d].push_back((int32_t)(c * nb + b));
-            }
-        }
-      std::vector<int32_t> off(1, 0), ent;
-      for (int64_t i = 0; i < nf; ++i)
-        {
-          for (int32_t e : at[(size_t)fin[(size_t)i]])
-            ent.push_back(e);
-          off.push_back((int32_t)ent.size());
-        }
-      for (int32_t **q : {&mg->d_rg_off, &mg->d_rg_ent})
-        if (*q)
-          {
-            HIP_THROW(hipStreamSynchronize(s));
-            HIP_THROW(hipFree(*q));
-            *q = nullptr;
-          }
-      HIP_THROW(hipMalloc((void **)&mg->d_rg_off, off.size() * 4));
-      HIP_THROW(hipMalloc((void **)&mg->d_rg_ent, std::max<size_t>(1, ent.size()) * 4));
-      HIP_THROW(hipMemcpy(mg->d_rg_off, off.data(), off.size() * 4, hipMemcpyHostToDevice));
-      if (!ent.empty())
-        HIP_THROW(hipMemcpy(mg->d_rg_ent, ent.data(), ent.size() * 4, hipMemcpyHostToDevice));
-    }
+    cond_tables(fin);
   const auto t3 = std::chrono::steady_clock::now();
   auto       ms = [](auto a, auto b) {
     return std::chrono::duration<double, std::milli>(b - a).count();
@@ -1879,8 +1973,6 @@ coarse_lu_setup_t(glsMG_ *mg, hipStream_t s)
   // per coarse solve; the Re3900 r0..r2 V-cycle differs from the FP64-stored
   // inverse's by 2.1e-7 (relative l2), the FP32 level arithmetic's own
   // round-off.  GLS_COARSE_INV_F32=0 keeps the FP64 inverse.
-  const char *e32 = getenv("GLS_COARSE_INV_F32");
-  mg->inv_f32     = !(e32 && e32[0] == '0') && mg->prec == GLS_F32;
   if (mg->inv_f32)
     {
       const int64_t ld = mg->ld_free;
@@ -1932,6 +2024,25 @@ void
 coarse_lu_solve_t(glsMG_ *mg, hipStream_t s)
 {
   const int64_t n = mg->ops[0]->n_dofs, nf = mg->n_free, ld = mg->ld_free;
+  if (mg->nd)
+    {
+      // the condensed (or gathered) right-hand side in FP64, the two sweeps
+      // over the elimination tree, the cells' interior dofs
+      if (mg->cond)
+        cond_rhs_t<T, double>(mg, mg->d_rhs, s);
+      else
+        {
+          copy_words(mg->sol[0], mg->def[0], n * (int64_t)sizeof(T) / 4, s);
+          hipLaunchKernelGGL(k_gather_free<T>, g1(nf), dim3(256), 0, s, mg->d_rhs,
+                             (const T *)mg->def[0], (const int32_t *)mg->d_free_in, nf);
+          HIP_THROW(hipGetLastError());
+        }
+      gls::nd_solver_solve(mg->nd, mg->d_rhs, mg->sol[0], std::is_same<T, double>::value,
+                           mg->d_free, s);
+      if (mg->cond)
+        cond_post_t<T>(mg, s);
+      return;
+    }
   if (mg->inv_f32)
     {
       // sol = def (constrained dofs: x_c = b_c, their rows of A are the
@@ -2650,6 +2761,7 @@ gls_mg_destroy(glsMG mg)
     rocblas_destroy_handle(mg->blas);
   if (mg->amg)
     gls_amg_destroy(mg->amg);
+  gls::nd_solver_destroy(mg->nd);
   if (mg->amg_io)
     (void)hipFree(mg->amg_io);
   mg->stage.release();
@@ -2795,6 +2907,66 @@ gls_mg_setup(glsMG mg, void *stream)
     }
   HIP_THROW(hipStreamSynchronize(s));
   mg->setup_done = true;
+  GLS_CATCH
+}
+
+glsStatus
+gls_mg_set_coarse_direct(glsMG mg, int method, int max_leaf_cells)
+{
+  GLS_TRY
+  if (!mg)
+    throw std::runtime_error("gls_mg_set_coarse_direct: null handle");
+  if (method != GLS_COARSE_DENSE && method != GLS_COARSE_ND)
+    throw std::runtime_error("gls_mg_set_coarse_direct: unknown method");
+  if (max_leaf_cells < 0)
+    throw std::runtime_error("gls_mg_set_coarse_direct: negative max_leaf_cells");
+  if (mg->desc.coarse_n_iterations >= 0 || mg->desc.coarse_amg)
+    throw std::runtime_error("gls_mg_set_coarse_direct: the coarse solver is not the direct one "
+                             "(coarse_n_iterations < 0)");
+  if (mg->partitioned)
+    throw std::runtime_error("gls_mg_set_coarse_direct: partitioned levels");
+  if (mg->setup_done)
+    throw std::runtime_error("gls_mg_set_coarse_direct: call it before gls_mg_setup");
+  mg->coarse_method = method;
+  mg->nd_leaf_cells = max_leaf_cells;
+  GLS_CATCH
+}
+
+glsStatus
+gls_mg_coarse_direct_info(glsMG mg, glsCoarseDirectInfo *info)
+{
+  GLS_TRY
+  if (!mg || !info)
+    throw std::runtime_error("gls_mg_coarse_direct_info: null argument");
+  if (mg->desc.coarse_n_iterations >= 0 || mg->desc.coarse_amg)
+    throw std::runtime_error("gls_mg_coarse_direct_info: the coarse solver is not the direct one");
+  *info           = glsCoarseDirectInfo{};
+  info->requested = mg->coarse_method;
+  info->max_leaf_cells =
+    mg->nd_leaf_cells > 0 ? mg->nd_leaf_cells : ND_DEFAULT_LEAF_CELLS;
+  info->n_free = mg->n_free;
+  if (mg->nd)
+    {
+      const gls::NdPlan &p = gls::nd_solver_plan(mg->nd);
+      info->method         = GLS_COARSE_ND;
+      info->tree_nodes     = (int)p.nodes.size();
+      info->depth          = p.depth;
+      info->max_own        = p.max_own;
+      info->max_boundary   = p.max_boundary;
+      info->plan_ms        = mg->nd_plan_ms;
+      gls::nd_solver_stats(mg->nd, &info->stored_entries, &info->stored_bytes, &info->factor_ms,
+                           &info->narrow_ms);
+    }
+  else
+    {
+      info->method     = GLS_COARSE_DENSE;
+      info->tree_nodes = info->depth = mg->n_free > 0 ? 1 : 0;
+      info->max_own    = (int)mg->n_free;
+      info->stored_entries = mg->n_free * (mg->inv_f32 ? mg->ld_free : mg->n_free);
+      info->stored_bytes   = info->stored_entries * (mg->inv_f32 ? 4 : 8);
+      info->factor_ms      = mg->coarse_setup_ms[0] + mg->coarse_setup_ms[1] +
+                        mg->coarse_setup_ms[2];
+    }
   GLS_CATCH
 }
 

@@ -51,7 +51,11 @@ EXPORTS = [
     "gls_op_set_outflow_target",
     "gls_op_set_force_faces", "gls_op_surface_force", "gls_op_surface_force_faces",
     "gls_op_set_probe_points", "gls_op_probe", "gls_dist_surface_force", "gls_dist_probe",
+    "gls_mg_set_coarse_direct", "gls_mg_coarse_direct_info",
+    "gls_nd_plan_create", "gls_nd_plan_destroy", "gls_nd_plan_info", "gls_nd_plan_node",
 ]
+
+GLS_COARSE_DENSE, GLS_COARSE_ND = 0, 1
 
 GLS_MEM_DEVICE, GLS_MEM_HOST = 0, 1
 
@@ -100,6 +104,27 @@ class MGDesc(C.Structure):
                 ("compute_evs_n_levels", C.c_int), ("coarse_iterate", C.c_int),
                 ("coarse_reltol", C.c_double), ("coarse_maxiter", C.c_int),
                 ("coarse_amg", C.c_int), ("amg", AMGParams)]
+
+
+class CoarseDirectInfo(C.Structure):
+    _fields_ = [("method", C.c_int), ("requested", C.c_int), ("max_leaf_cells", C.c_int),
+                ("n_free", C.c_int64), ("tree_nodes", C.c_int), ("depth", C.c_int),
+                ("max_own", C.c_int), ("max_boundary", C.c_int),
+                ("stored_entries", C.c_int64), ("stored_bytes", C.c_int64),
+                ("plan_ms", C.c_double), ("factor_ms", C.c_double), ("narrow_ms", C.c_double)]
+
+
+class NdPlanInfo(C.Structure):
+    _fields_ = [("n_dofs", C.c_int64), ("n_tree_nodes", C.c_int), ("depth", C.c_int),
+                ("sum_own", C.c_int64), ("stored_entries", C.c_int64),
+                ("max_own", C.c_int), ("max_boundary", C.c_int)]
+
+
+class NdPlanNode(C.Structure):
+    _fields_ = [("parent", C.c_int), ("child", C.c_int * 2), ("level", C.c_int),
+                ("n_own", C.c_int), ("n_boundary", C.c_int), ("n_cells", C.c_int),
+                ("own", C.POINTER(C.c_int32)), ("boundary", C.POINTER(C.c_int32)),
+                ("map", C.POINTER(C.c_int32)), ("cells", C.POINTER(C.c_int32))]
 
 
 class DistDesc(C.Structure):
@@ -218,6 +243,13 @@ def lib():
         L.gls_dist_mg_vcycle.argtypes = [vp, C.c_int, vp, vp, vp]
         L.gls_dist_gmres_solve.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp, vp]
         L.gls_discover_bricks.argtypes = [C.c_int, C.c_int, i64, vp, vp, vp]
+        L.gls_mg_set_coarse_direct.argtypes = [vp, C.c_int, C.c_int]
+        L.gls_mg_coarse_direct_info.argtypes = [vp, C.POINTER(CoarseDirectInfo)]
+        L.gls_nd_plan_create.argtypes = [vp, i64, C.c_int, i64, vp, C.c_int, C.POINTER(vp)]
+        L.gls_nd_plan_destroy.argtypes = [vp]
+        L.gls_nd_plan_destroy.restype = None
+        L.gls_nd_plan_info.argtypes = [vp, C.POINTER(NdPlanInfo)]
+        L.gls_nd_plan_node.argtypes = [vp, C.c_int, C.POINTER(NdPlanNode)]
         L.gls_last_error.restype = C.c_char_p
         L.gls_timer_enable.argtypes = [C.c_int, C.POINTER(C.c_int)]
         L.gls_timer_reset.argtypes = []
@@ -988,6 +1020,42 @@ class AMG:
             pass
 
 
+class NdPlan:
+    """The nested-dissection plan of the "nd" direct coarse solver on its own
+    (host only, no GPU): the elimination tree over the cells of a cell ->
+    node table, node_dofs[n] dofs of mesh node n taking part (plan dofs are
+    numbered node by node).  nodes[t]: dict of parent, child, level, own (I),
+    boundary (B), map (position of each B entry in the parent's I then B) and
+    a leaf's cells; node 0 is the root."""
+
+    def __init__(self, cell_nodes, node_dofs, max_leaf_cells):
+        cn = np.ascontiguousarray(cell_nodes, dtype=np.uint32)
+        nd = np.ascontiguousarray(node_dofs, dtype=np.int32)
+        h = C.c_void_p()
+        _check(lib().gls_nd_plan_create(cn.ctypes.data, cn.shape[0], cn.shape[1], nd.shape[0],
+                                        nd.ctypes.data, int(max_leaf_cells), C.byref(h)))
+        try:
+            i = NdPlanInfo()
+            _check(lib().gls_nd_plan_info(h, C.byref(i)))
+            self.info = {"n_dofs": i.n_dofs, "tree_nodes": i.n_tree_nodes, "depth": i.depth,
+                         "sum_own": i.sum_own, "stored_entries": i.stored_entries,
+                         "max_own": i.max_own, "max_boundary": i.max_boundary}
+            self.nodes = []
+            for t in range(i.n_tree_nodes):
+                n = NdPlanNode()
+                _check(lib().gls_nd_plan_node(h, t, C.byref(n)))
+
+                def arr(p, k):
+                    return np.array(p[:k], dtype=np.int32)
+                self.nodes.append({"parent": n.parent, "child": (n.child[0], n.child[1]),
+                                   "level": n.level, "own": arr(n.own, n.n_own),
+                                   "boundary": arr(n.boundary, n.n_boundary),
+                                   "map": arr(n.map, n.n_boundary),
+                                   "cells": arr(n.cells, n.n_cells)})
+        finally:
+            lib().gls_nd_plan_destroy(h)
+
+
 class Multigrid:
     """PreconditionerGMG (multigrid.h:61-141) over the C-ABI: level operators
     (MGNumber = float by default), damped-Jacobi relaxation smoother with a
@@ -996,7 +1064,10 @@ class Multigrid:
     def __init__(self, level_ops, child_lattices, smoothing_n_iterations=5,
                  smoothing_eig_n_iterations=20, smoothing_range=20.0, coarse_n_iterations=20,
                  outer_precision="f64", compute_evs_n_levels=0, coarse_iterate=False,
-                 coarse_reltol=1e-4, coarse_maxiter=10000, coarse_amg=None):
+                 coarse_reltol=1e-4, coarse_maxiter=10000, coarse_amg=None,
+                 coarse_direct="dense", coarse_leaf_cells=None):
+        if coarse_direct not in ("dense", "nd"):
+            raise ValueError(f"coarse_direct: 'dense' or 'nd', not {coarse_direct!r}")
         self.ops = list(level_ops)
         self._child = [None] + [np.ascontiguousarray(c, dtype=np.uint32)
                                 for c in child_lattices]
@@ -1018,6 +1089,35 @@ class Multigrid:
         _check(lib().gls_mg_create(C.byref(self.desc), C.cast(arr, C.c_void_p),
                                    C.cast(ch, C.c_void_p), C.byref(h)))
         self.h = h
+        if coarse_direct != "dense" or coarse_leaf_cells is not None:
+            # the form of the direct coarse solver (coarse_n_iterations < 0):
+            # "nd" = nested dissection over the coarse cells, coarse_leaf_cells
+            # cells per leaf of its tree (None: the library's default)
+            _check(lib().gls_mg_set_coarse_direct(
+                self.h, GLS_COARSE_ND if coarse_direct == "nd" else GLS_COARSE_DENSE,
+                int(coarse_leaf_cells or 0)))
+
+    def set_coarse_direct(self, coarse_direct, coarse_leaf_cells=None):
+        """The direct coarse solver's form ("dense" | "nd"), before setup()."""
+        _check(lib().gls_mg_set_coarse_direct(
+            self.h, GLS_COARSE_ND if coarse_direct == "nd" else GLS_COARSE_DENSE,
+            int(coarse_leaf_cells or 0)))
+
+    def coarse_direct_info(self):
+        """The direct coarse solver after the last setup(): method ("dense" |
+        "nd": the one that is live, "dense" after a fallback), requested, nf,
+        tree_nodes, depth, max_own, max_boundary, stored_entries,
+        stored_bytes, and the wall ms of the last setup (plan_ms: 0 when the
+        plan was reused; factor_ms: fronts + factorisation; narrow_ms: the
+        stored copies)."""
+        i = CoarseDirectInfo()
+        _check(lib().gls_mg_coarse_direct_info(self.h, C.byref(i)))
+        names = {GLS_COARSE_DENSE: "dense", GLS_COARSE_ND: "nd"}
+        return {"method": names[i.method], "requested": names[i.requested],
+                "max_leaf_cells": i.max_leaf_cells, "nf": i.n_free, "tree_nodes": i.tree_nodes,
+                "depth": i.depth, "max_own": i.max_own, "max_boundary": i.max_boundary,
+                "stored_entries": i.stored_entries, "stored_bytes": i.stored_bytes,
+                "plan_ms": i.plan_ms, "factor_ms": i.factor_ms, "narrow_ms": i.narrow_ms}
 
     def __del__(self):
         try:

@@ -452,6 +452,64 @@ glsStatus gls_mg_coarse_amg(glsMG mg, glsAMG *amg, double *setup_ms);
  * interior dofs statically condensed, scattered per cell colour), of getrf
  * and of the inverse (trtri + trsm), and the number of cell colours */
 glsStatus gls_mg_coarse_setup_times(glsMG mg, double *ms3, int *n_colors);
+/* The form of the direct coarse solver (coarse_n_iterations < 0; an error
+ * otherwise), chosen before the first gls_mg_setup (an error after it).
+ * GLS_COARSE_DENSE (default): the dense inverse of the free-dof block.
+ * GLS_COARSE_ND: a multifrontal nested-dissection factorisation over the
+ * coarse cells with every pivot block stored as an explicit inverse, the
+ * solve two sweeps of batched GEMVs over the tree levels.
+ * max_leaf_cells: cells per leaf of the elimination tree (0: the default).
+ * Pivoting is confined to the pivot blocks; a singular block makes the setup
+ * fall back to the dense solver (one line on stderr). */
+#define GLS_COARSE_DENSE 0
+#define GLS_COARSE_ND 1
+glsStatus gls_mg_set_coarse_direct(glsMG mg, int method, int max_leaf_cells);
+typedef struct
+{
+  int     method;         /* the solver that is live after the last setup     */
+  int     requested;      /* what gls_mg_set_coarse_direct asked for          */
+  int     max_leaf_cells;
+  int64_t n_free;         /* dofs of the factorised block (cell interiors
+                             condensed away where that is on)                 */
+  int     tree_nodes, depth; /* elimination tree (dense: 1, 1)                */
+  int     max_own, max_boundary; /* largest pivot block / boundary set        */
+  int64_t stored_entries; /* factor entries the solve reads, padding included */
+  int64_t stored_bytes;
+  double  plan_ms;        /* wall ms of the last setup: the plan (0 when it
+                             was reused),                                     */
+  double  factor_ms;      /* fronts + factorisation,                          */
+  double  narrow_ms;      /* the stored (FP32) copies                         */
+} glsCoarseDirectInfo;
+glsStatus gls_mg_coarse_direct_info(glsMG mg, glsCoarseDirectInfo *info);
+
+/* The nested-dissection plan on its own (host only): the elimination tree
+ * over the cells from the cell -> node table, node_dofs[n] dofs of mesh node
+ * n taking part (numbered node by node).  Node 0 is the root.  The arrays of
+ * gls_nd_plan_node live until gls_nd_plan_destroy. */
+typedef struct glsNdPlan_ *glsNdPlan;
+typedef struct
+{
+  int64_t n_dofs;
+  int     n_tree_nodes, depth;
+  int64_t sum_own;        /* sum of |I| (= n_dofs)                            */
+  int64_t stored_entries; /* sum of |I|^2 + 2 |I| |B|                         */
+  int     max_own, max_boundary;
+} glsNdPlanInfo;
+typedef struct
+{
+  int            parent, child[2], level; /* -1: none                         */
+  int            n_own, n_boundary, n_cells;
+  const int32_t *own;      /* I, ascending                                    */
+  const int32_t *boundary; /* B, ascending                                    */
+  const int32_t *map;      /* [n_boundary] position in the parent's I then B  */
+  const int32_t *cells;    /* a leaf's cells, ascending                       */
+} glsNdPlanNode;
+glsStatus gls_nd_plan_create(const uint32_t *cell_nodes, int64_t n_cells, int nodes_per_cell,
+                             int64_t n_nodes, const int32_t *node_dofs, int max_leaf_cells,
+                             glsNdPlan *out);
+void      gls_nd_plan_destroy(glsNdPlan plan);
+glsStatus gls_nd_plan_info(glsNdPlan plan, glsNdPlanInfo *info);
+glsStatus gls_nd_plan_node(glsNdPlan plan, int node, glsNdPlanNode *out);
 /* one V-cycle on the finest level: dst = V(src) (PreconditionMG::vmult) */
 glsStatus gls_mg_vcycle(glsMG mg, void *dst, const void *src, void *stream);
 /* caller vector layout of gls_mg_vcycle's dst / src (as gls_op_set_vector_

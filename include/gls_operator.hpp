@@ -363,6 +363,23 @@ public:
           "gls_mg_set_vector_layout");
   }
 
+  // the direct coarse solver's form (desc.coarse_n_iterations < 0), before
+  // the first initialize(): GLS_COARSE_DENSE or GLS_COARSE_ND (nested
+  // dissection over the coarse cells, max_leaf_cells = 0: the default)
+  void
+  set_coarse_direct(int method, int max_leaf_cells = 0)
+  {
+    check(gls_mg_set_coarse_direct(h, method, max_leaf_cells), "gls_mg_set_coarse_direct");
+  }
+
+  glsCoarseDirectInfo
+  coarse_direct_info() const
+  {
+    glsCoarseDirectInfo info;
+    check(gls_mg_coarse_direct_info(h, &info), "gls_mg_coarse_direct_info");
+    return info;
+  }
+
   // PreconditionerGMG::initialize (multigrid.cc:247-370)
   void initialize(void *stream = nullptr) { check(gls_mg_setup(h, stream), "gls_mg_setup"); }
 
