@@ -26,10 +26,17 @@
 //   * Chebyshev smoothing of degree smoother_sweeps on D^-1 A over
 //     [1.1 lambda / alpha, 1.1 lambda], alpha = chebyshev_alpha (deal.II's
 //     10; ML's own default 30) -- ML's default smoother for the elliptic
-//     defaults; the decks' ILU smoother is sequential and substituted by it.
+//     defaults, and this library's default for the decks that ask for ILU;
+//   * on request (gls_amg_create_ilu: the decks' non-default parameters,
+//     smoother_type = coarse_type = "ILU", multigrid.cc:403-413) ILU(k)
+//     smoothing instead: smoother_sweeps steps of x += M^-1 (f - A x) with
+//     M = L U of the level matrix (csrc/ilu.hip; the first pre-smoothing
+//     step from the zero start is x = M^-1 f), and the same steps as the
+//     coarsest solve instead of the dense inverse.
 // Setup on the host (as ML's); the V-cycle on the device: CSR SpMV kernels
 // with the Chebyshev update fused, one launch per sweep.  tests/amg_ref.py
-// restates the same algorithm with scipy for the parity tests.
+// restates the same algorithm with scipy for the parity tests, tests/
+// ilu_ref.py its ILU form.
 #include "../../include/gls_op.h"
 #include "common.h"
 
@@ -348,6 +355,22 @@ __global__ void __launch_bounds__(256)
     }
 }
 
+// res = f - A x
+template <int G>
+__global__ void __launch_bounds__(256)
+  k_residual_plain(const int32_t *__restrict__ rp, const int32_t *__restrict__ ci,
+                   const double *__restrict__ v, const double *__restrict__ x,
+                   const double *__restrict__ f, double *__restrict__ res, int64_t n)
+{
+  const int64_t r    = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / G;
+  const int     lane = threadIdx.x & (G - 1);
+  if (r >= n)
+    return;
+  const double s = row_dot<G>(rp, ci, v, x, nullptr, r, lane);
+  if (lane == 0)
+    res[r] = f[r] - s;
+}
+
 // y = M x (add = 0) or y += M x (add = 1)
 template <int G>
 __global__ void __launch_bounds__(256)
@@ -477,6 +500,7 @@ struct AmgLevel
   double *dinv = nullptr, *x = nullptr, *d = nullptr, *f = nullptr, *r = nullptr,
          *x2 = nullptr, *d2 = nullptr;
   double  lambda = 0; // spectral radius estimate of D^-1 A
+  glsILU  ilu    = nullptr; // ILU smoother / coarsest solve (gls_amg_create_ilu)
 };
 } // namespace gls
 
@@ -487,6 +511,7 @@ struct glsAMG_
   double                     *d_inv = nullptr; // coarsest: row-major dense inverse
   int64_t                     n_coarse = 0;
   int                         device   = 0;
+  glsAMGIluParams             ilu{};   // all zero: the Chebyshev / dense form
 };
 
 namespace gls
@@ -575,19 +600,92 @@ vcycle_level(glsAMG_ *amg, size_t l, hipStream_t st)
   chebyshev(amg, L, false, st);
   HIP_THROW(hipGetLastError());
 }
-} // namespace
-} // namespace gls
 
-extern "C" {
+void
+check_ilu(glsStatus st)
+{
+  if (st != 0)
+    throw std::runtime_error(std::string("amg: ") + gls_last_error());
+}
+
+// smoother_sweeps ILU steps on level L, the iterate in L.x (plain, no
+// pending part): x = M^-1 f from the zero start, else x += M^-1 (f - A x)
+void
+ilu_steps(glsAMG_ *amg, AmgLevel &L, bool zero_start, hipStream_t st)
+{
+  const int     s = std::max(1, amg->prm.smoother_sweeps);
+  const int64_t n = L.A.n;
+  for (int k = 0; k < s; ++k)
+    if (k == 0 && zero_start)
+      check_ilu(gls_ilu_vmult(L.ilu, L.x, L.f, st));
+    else
+      {
+        GLS_ROWS(k_residual_plain, L.A, st, L.A.rp, L.A.ci, L.A.v, L.x, L.f, L.r, n);
+        check_ilu(gls_ilu_vmult(L.ilu, L.d, L.r, st));
+        hipLaunchKernelGGL(k_add2, elem_grid(n), dim3(256), 0, st, L.x, L.d, L.x2, n);
+        std::swap(L.x, L.x2);
+      }
+  HIP_THROW(hipGetLastError());
+}
+
+// the smoother of the ILU form's cycle: ILU steps, or (smoother_ilu = 0)
+// the Chebyshev steps with their pending pair summed into L.x
+void
+smooth_plain(glsAMG_ *amg, AmgLevel &L, bool zero_start, hipStream_t st)
+{
+  if (L.ilu)
+    return ilu_steps(amg, L, zero_start, st);
+  chebyshev(amg, L, zero_start, st);
+  hipLaunchKernelGGL(k_add2, elem_grid(L.A.n), dim3(256), 0, st, L.x, L.d, L.x2, L.A.n);
+  std::swap(L.x, L.x2);
+  HIP_THROW(hipGetLastError());
+}
+
+// the V-cycle of the ILU form (gls_amg_create_ilu): every level's iterate
+// plain in L.x
+void
+vcycle_level_ilu(glsAMG_ *amg, size_t l, hipStream_t st)
+{
+  AmgLevel &L = amg->lv[l];
+  if (l + 1 == amg->lv.size())
+    {
+      if (L.ilu)
+        ilu_steps(amg, L, true, st);
+      else if (amg->d_inv)
+        hipLaunchKernelGGL(k_dense_gemv, rows_grid(L.A.n), dim3(256), 0, st, amg->d_inv, L.f, L.x,
+                           L.A.n);
+      else
+        smooth_plain(amg, L, true, st);
+      HIP_THROW(hipGetLastError());
+      return;
+    }
+  AmgLevel &C = amg->lv[l + 1];
+  smooth_plain(amg, L, true, st);
+  GLS_ROWS(k_residual_plain, L.A, st, L.A.rp, L.A.ci, L.A.v, L.x, L.f, L.r, L.A.n);
+  GLS_ROWS(k_spmv, L.R, st, L.R.rp, L.R.ci, L.R.v, L.r, C.f, 0, L.R.n);
+  vcycle_level_ilu(amg, l + 1, st);
+  GLS_ROWS(k_spmv, L.P, st, L.P.rp, L.P.ci, L.P.v, C.x, L.x, 1, L.P.n);
+  smooth_plain(amg, L, false, st);
+  HIP_THROW(hipGetLastError());
+}
+
+bool
+ilu_form(const glsAMG_ *amg)
+{
+  return amg->ilu.smoother_ilu || amg->ilu.coarse_ilu;
+}
 
 glsStatus
-gls_amg_create(int64_t n, const int64_t *row_ptr, const int64_t *cols, const double *vals,
-               const glsAMGParams *prm, glsAMG *out)
+amg_create(int64_t n, const int64_t *row_ptr, const int64_t *cols, const double *vals,
+           const glsAMGParams *prm, const glsAMGIluParams *ilu_prm, glsAMG *out)
 {
   GLS_TRY
   using namespace gls;
   if (!row_ptr || !cols || !vals || !prm || !out || n <= 0)
     throw std::runtime_error("gls_amg_create: invalid argument");
+  if (ilu_prm && (ilu_prm->fill_level < 0 || !std::isfinite(ilu_prm->atol) ||
+                  !std::isfinite(ilu_prm->rtol)))
+    throw std::runtime_error("gls_amg_create_ilu: invalid ILU parameters");
   const int b = prm->block_size;
   if (b < 1 || n % b != 0 || prm->smoother_sweeps < 1 || prm->coarse_max_size < 1 ||
       prm->max_levels < 1 || !(prm->threshold >= 0))
@@ -605,6 +703,8 @@ gls_amg_create(int64_t n, const int64_t *row_ptr, const int64_t *cols, const dou
     }
   } guard{amg};
   amg->prm = *prm;
+  if (ilu_prm)
+    amg->ilu = *ilu_prm;
   HIP_THROW(hipGetDevice(&amg->device));
   HostCSR A;
   A.n = A.m = n;
@@ -722,7 +822,19 @@ gls_amg_create(int64_t n, const int64_t *row_ptr, const int64_t *cols, const dou
   // reached) is smoothed instead of factorised (a dense matrix of it would
   // need n^2 doubles on the host and the device)
   amg->n_coarse = hA.back().n;
-  if (hA.back().n <= amg_dense_limit(*prm))
+  // the ILU form: a factor of every smoothed level's matrix (smoother_ilu)
+  // and of the coarsest one (coarse_ilu; no dense inverse then)
+  for (size_t l = 0; l < amg->lv.size() && ilu_form(amg); ++l)
+    {
+      const bool coarsest = l + 1 == amg->lv.size();
+      if (!(coarsest ? amg->ilu.coarse_ilu : amg->ilu.smoother_ilu))
+        continue;
+      const HostCSR             &Al = hA[l];
+      const std::vector<int64_t> ci64(Al.ci.begin(), Al.ci.end());
+      const glsILUParams         ip{amg->ilu.fill_level, amg->ilu.atol, amg->ilu.rtol};
+      check_ilu(gls_ilu_create(Al.n, Al.rp.data(), ci64.data(), Al.v.data(), &ip, &amg->lv[l].ilu));
+    }
+  if (!amg->ilu.coarse_ilu && hA.back().n <= amg_dense_limit(*prm))
   {
     const HostCSR &Ac = hA.back();
     const int64_t  nc = Ac.n;
@@ -774,6 +886,29 @@ gls_amg_create(int64_t n, const int64_t *row_ptr, const int64_t *cols, const dou
   *out    = amg;
   GLS_CATCH
 }
+} // namespace
+} // namespace gls
+
+extern "C" {
+
+glsStatus
+gls_amg_create(int64_t n, const int64_t *row_ptr, const int64_t *cols, const double *vals,
+               const glsAMGParams *prm, glsAMG *out)
+{
+  return gls::amg_create(n, row_ptr, cols, vals, prm, nullptr, out);
+}
+
+glsStatus
+gls_amg_create_ilu(int64_t n, const int64_t *row_ptr, const int64_t *cols, const double *vals,
+                   const glsAMGParams *prm, const glsAMGIluParams *ilu, glsAMG *out)
+{
+  if (!ilu)
+    {
+      gls::set_error("gls_amg_create_ilu: null ILU parameters");
+      return 1;
+    }
+  return gls::amg_create(n, row_ptr, cols, vals, prm, ilu, out);
+}
 
 void
 gls_amg_destroy(glsAMG amg)
@@ -785,6 +920,7 @@ gls_amg_destroy(glsAMG amg)
       gls::free_csr(L.A), gls::free_csr(L.P), gls::free_csr(L.R);
       for (double *p : {L.dinv, L.x, L.d, L.f, L.r, L.x2, L.d2})
         (void)hipFree(p);
+      gls_ilu_destroy(L.ilu);
     }
   (void)hipFree(amg->d_inv);
   delete amg;
@@ -807,7 +943,10 @@ gls_amg_vmult(glsAMG amg, double *dst, const double *src, void *stream)
   L0.f             = const_cast<double *>(src);
   try
     {
-      vcycle_level(amg, 0, st);
+      if (ilu_form(amg))
+        vcycle_level_ilu(amg, 0, st);
+      else
+        vcycle_level(amg, 0, st);
     }
   catch (...)
     {
@@ -815,7 +954,7 @@ gls_amg_vmult(glsAMG amg, double *dst, const double *src, void *stream)
       throw;
     }
   L0.f = f0;
-  if (amg->lv.size() > 1)
+  if (amg->lv.size() > 1 && !ilu_form(amg))
     hipLaunchKernelGGL(k_add2, elem_grid(n), dim3(256), 0, st, L0.x, L0.d, dst, n);
   else
     HIP_THROW(hipMemcpyAsync(dst, L0.x, (size_t)n * 8, hipMemcpyDeviceToDevice, st));

@@ -92,14 +92,30 @@ check(glsStatus st, const char *what)
 
 } // namespace
 
-extern "C" glsStatus
-gls_gmres_solve(glsOp op, glsMG mg, const glsGMRESDesc *desc, void *x_, const void *b_,
-                glsGMRESResult *result, void *stream)
+namespace gls
+{
+// csrc/ilu.hip: gls_ilu_vmult on the factor's device without the scope
+void    ilu_apply(glsILU_ *ilu, double *dst, const double *src, hipStream_t st);
+int64_t ilu_size(const glsILU_ *ilu);
+} // namespace gls
+
+// the solver behind gls_gmres_solve (kind GLS_PREC_MG, prec a glsMG or null:
+// identity) and gls_gmres_solve_prec
+static glsStatus
+gmres_solve(glsOp op, int kind, void *prec, const glsGMRESDesc *desc, void *x_, const void *b_,
+            glsGMRESResult *result, void *stream)
 {
   GLS_TRY
   gls::Section sec_("gmres::solve", (hipStream_t)stream);
   if (!op || !desc || !x_ || !b_)
     throw std::runtime_error("gls_gmres_solve: null argument");
+  if (kind != GLS_PREC_MG && kind != GLS_PREC_ILU && kind != GLS_PREC_AMG)
+    throw std::runtime_error("gls_gmres_solve_prec: unknown preconditioner kind");
+  if (kind != GLS_PREC_MG && !prec)
+    throw std::runtime_error("gls_gmres_solve_prec: null preconditioner");
+  const glsMG  mg  = kind == GLS_PREC_MG ? (glsMG)prec : nullptr;
+  const glsILU ilu = kind == GLS_PREC_ILU ? (glsILU)prec : nullptr;
+  const glsAMG amg = kind == GLS_PREC_AMG ? (glsAMG)prec : nullptr;
   if (op->prec != GLS_F64)
     throw std::runtime_error("gls_gmres_solve: the outer operator must be FP64 "
                              "(LinearSolverGMRES works on VectorType<double>)");
@@ -110,6 +126,22 @@ gls_gmres_solve(glsOp op, glsMG mg, const glsGMRESDesc *desc, void *x_, const vo
     throw std::runtime_error("gls_gmres_solve: max_n_tmp_vectors must be >= 3");
   if (mg)
     gls::mg_check_outer(mg, op); // FP64 outer vectors of op's size, set up
+  // ILU / AMG of gls_op_system_matrix: its rows are the node-major dofs the
+  // Krylov vectors hold on the device (the caller layout is staged at the
+  // solve's ends), so the factor applies to them as they are
+  if (ilu && gls::ilu_size(ilu) != op->n_dofs)
+    throw std::runtime_error("gls_gmres_solve_prec: the ILU is not of the operator's size");
+  if (amg)
+    {
+      int     nl = 0;
+      int64_t sizes[64];
+      check(gls_amg_info(amg, &nl, nullptr, nullptr, nullptr), "gls_amg_info");
+      if (nl < 1 || nl > 64)
+        throw std::runtime_error("gls_gmres_solve_prec: AMG hierarchy out of range");
+      check(gls_amg_info(amg, &nl, sizes, nullptr, nullptr), "gls_amg_info");
+      if (sizes[0] != op->n_dofs)
+        throw std::runtime_error("gls_gmres_solve_prec: the AMG is not of the operator's size");
+    }
   // the operator's device for the whole solve (staging buffers included),
   // the caller's current device restored on return
   gls::DeviceScope dev(op->device);
@@ -201,6 +233,16 @@ gls_gmres_solve(glsOp op, glsMG mg, const glsGMRESDesc *desc, void *x_, const vo
       {
         gls::Section sc("gmg::vmult", s);
         gls::mg_vcycle_device(mg, dst, src, s);
+      }
+    else if (ilu)
+      {
+        gls::Section sc("ilu::vmult", s);
+        gls::ilu_apply(ilu, dst, src, s);
+      }
+    else if (amg)
+      {
+        gls::Section sc("amg::vmult", s);
+        check(gls_amg_vmult(amg, dst, src, s), "gls_amg_vmult");
       }
     else
       HIP_THROW(hipMemcpyAsync(dst, src, n * sizeof(double), hipMemcpyDeviceToDevice, s));
@@ -605,4 +647,18 @@ gls_gmres_solve(glsOp op, glsMG mg, const glsGMRESDesc *desc, void *x_, const vo
                              " iterations (residual " + std::to_string(res) + " > " +
                              std::to_string(tol) + ")");
   GLS_CATCH
+}
+
+extern "C" glsStatus
+gls_gmres_solve(glsOp op, glsMG mg, const glsGMRESDesc *desc, void *x_, const void *b_,
+                glsGMRESResult *result, void *stream)
+{
+  return gmres_solve(op, GLS_PREC_MG, mg, desc, x_, b_, result, stream);
+}
+
+extern "C" glsStatus
+gls_gmres_solve_prec(glsOp op, int kind, void *prec, const glsGMRESDesc *desc, void *x_,
+                     const void *b_, glsGMRESResult *result, void *stream)
+{
+  return gmres_solve(op, kind, prec, desc, x_, b_, result, stream);
 }

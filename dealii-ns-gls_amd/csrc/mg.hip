@@ -706,6 +706,17 @@ struct glsMG_
   glsAMG  amg      = nullptr;
   double *amg_io   = nullptr; // [2 n0] FP64 in / out of a direct AMG coarse solve
   double  amg_setup_ms = 0;
+  // its ILU form (gls_mg_set_coarse_amg_ilu; smoother / coarsest ILU(k))
+  bool            amg_ilu = false;
+  glsAMGIluParams amg_ilu_prm{};
+  // "gmg coarse grid solver": "ILU" (gls_mg_set_coarse_ilu, multigrid.cc:
+  // 434-447): ILU(k) of the coarse level's system matrix as the coarse
+  // preconditioner; created by the first gls_mg_setup, refactored on the
+  // same pattern by the later ones.  FP32 levels go through amg_io.
+  bool         coarse_ilu = false;
+  glsILUParams ilu_prm{};
+  glsILU       ilu          = nullptr;
+  double       ilu_setup_ms = 0;
 
   size_t
   ts() const
@@ -2094,13 +2105,36 @@ check_amg(glsStatus st)
     throw std::runtime_error(std::string("coarse AMG: ") + gls_last_error());
 }
 
+void
+check_ilu(glsStatus st)
+{
+  if (st != 0)
+    throw std::runtime_error(std::string("coarse ILU: ") + gls_last_error());
+}
+
 // the coarse "preconditioner" once: sol[0] from def[0] (multigrid.cc:465-489):
 // dense LU (< 0), identity (0) or relaxation sweeps (> 0)
 void
 coarse_apply(glsMG_ *mg, hipStream_t s, PendingReduce *pend = nullptr)
 {
   const size_t bytes = (size_t)mg->ops[0]->n_dofs * mg->ts();
-  if (mg->desc.coarse_amg)
+  if (mg->coarse_ilu)
+    {
+      // the ILU factor once (coarse_iterate = 0): in FP64
+      const int64_t n = mg->ops[0]->n_dofs;
+      if (mg->prec == GLS_F64)
+        check_ilu(gls_ilu_vmult(mg->ilu, (double *)mg->sol[0], (const double *)mg->def[0], s));
+      else
+        {
+          hipLaunchKernelGGL((k_convert<float, double>), g1(n), dim3(256), 0, s, mg->amg_io,
+                             (const float *)mg->def[0], n);
+          check_ilu(gls_ilu_vmult(mg->ilu, mg->amg_io + n, mg->amg_io, s));
+          hipLaunchKernelGGL((k_convert<double, float>), g1(n), dim3(256), 0, s,
+                             (float *)mg->sol[0], mg->amg_io + n, n);
+        }
+      HIP_THROW(hipGetLastError());
+    }
+  else if (mg->desc.coarse_amg)
     {
       // one AMG V-cycle as the coarse solver (coarse_iterate = 0): in FP64
       const int64_t n = mg->ops[0]->n_dofs;
@@ -2193,6 +2227,11 @@ coarse_gmres_t(glsMG_ *mg, hipStream_t s)
   // dst = P^{-1} src (through def[0] -> sol[0]); AMG: its V-cycle on the
   // FP64 vectors directly (the reference's Trilinos AMG on the FP64 matrix)
   auto prec = [&](double *dst, const double *src) {
+    if (mg->coarse_ilu) // the factor on the FP64 vectors directly, as the AMG
+      {
+        check_ilu(gls_ilu_vmult(mg->ilu, dst, src, s));
+        return;
+      }
     if (mg->desc.coarse_amg)
       {
         check_amg(gls_amg_vmult(mg->amg, dst, src, s));
@@ -2764,6 +2803,7 @@ gls_mg_destroy(glsMG mg)
   gls::nd_solver_destroy(mg->nd);
   if (mg->amg_io)
     (void)hipFree(mg->amg_io);
+  gls_ilu_destroy(mg->ilu);
   mg->stage.release();
   delete mg;
 }
@@ -2873,7 +2913,32 @@ gls_mg_setup(glsMG mg, void *stream)
         else
           mg->omega[l] = 1.0;
       }
-  if (mg->desc.coarse_amg)
+  if (mg->coarse_ilu)
+    {
+      // the coarse level's system matrix (FP64) and its ILU: the pattern
+      // never changes, so every setup after the first refactors
+      HIP_THROW(hipStreamSynchronize(s));
+      gls::Section sc("gmg::initialize::ilu", s);
+      const auto t0   = std::chrono::steady_clock::now();
+      glsOp      op0  = mg->ops[0];
+      int64_t    nnz  = 0;
+      if (gls_op_system_matrix(op0, &nnz, nullptr, nullptr, nullptr) != 0)
+        throw std::runtime_error(std::string("coarse ILU: ") + gls_last_error());
+      std::vector<int64_t> rp((size_t)op0->n_dofs + 1), ci((size_t)nnz);
+      std::vector<double>  va((size_t)nnz);
+      if (gls_op_system_matrix(op0, &nnz, rp.data(), ci.data(), va.data()) != 0)
+        throw std::runtime_error(std::string("coarse ILU: ") + gls_last_error());
+      if (mg->ilu)
+        check_ilu(gls_ilu_refactor(mg->ilu, va.data()));
+      else
+        check_ilu(gls_ilu_create(op0->n_dofs, rp.data(), ci.data(), va.data(), &mg->ilu_prm,
+                                 &mg->ilu));
+      if (!mg->amg_io)
+        HIP_THROW(hipMalloc((void **)&mg->amg_io, (size_t)2 * op0->n_dofs * 8));
+      mg->ilu_setup_ms =
+        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+  else if (mg->desc.coarse_amg)
     {
       // the coarse level's system matrix (FP64, constrained rows / columns
       // identity) and the AMG hierarchy on it
@@ -2890,8 +2955,12 @@ gls_mg_setup(glsMG mg, void *stream)
         throw std::runtime_error(std::string("coarse AMG: ") + gls_last_error());
       if (mg->amg)
         gls_amg_destroy(mg->amg), mg->amg = nullptr;
-      check_amg(gls_amg_create(op0->n_dofs, rp.data(), ci.data(), va.data(), &mg->desc.amg,
-                               &mg->amg));
+      if (mg->amg_ilu)
+        check_amg(gls_amg_create_ilu(op0->n_dofs, rp.data(), ci.data(), va.data(), &mg->desc.amg,
+                                     &mg->amg_ilu_prm, &mg->amg));
+      else
+        check_amg(gls_amg_create(op0->n_dofs, rp.data(), ci.data(), va.data(), &mg->desc.amg,
+                                 &mg->amg));
       if (!mg->amg_io)
         HIP_THROW(hipMalloc((void **)&mg->amg_io, (size_t)2 * op0->n_dofs * 8));
       mg->amg_setup_ms =
@@ -2920,7 +2989,7 @@ gls_mg_set_coarse_direct(glsMG mg, int method, int max_leaf_cells)
     throw std::runtime_error("gls_mg_set_coarse_direct: unknown method");
   if (max_leaf_cells < 0)
     throw std::runtime_error("gls_mg_set_coarse_direct: negative max_leaf_cells");
-  if (mg->desc.coarse_n_iterations >= 0 || mg->desc.coarse_amg)
+  if (mg->desc.coarse_n_iterations >= 0 || mg->desc.coarse_amg || mg->coarse_ilu)
     throw std::runtime_error("gls_mg_set_coarse_direct: the coarse solver is not the direct one "
                              "(coarse_n_iterations < 0)");
   if (mg->partitioned)
@@ -2938,7 +3007,7 @@ gls_mg_coarse_direct_info(glsMG mg, glsCoarseDirectInfo *info)
   GLS_TRY
   if (!mg || !info)
     throw std::runtime_error("gls_mg_coarse_direct_info: null argument");
-  if (mg->desc.coarse_n_iterations >= 0 || mg->desc.coarse_amg)
+  if (mg->desc.coarse_n_iterations >= 0 || mg->desc.coarse_amg || mg->coarse_ilu)
     throw std::runtime_error("gls_mg_coarse_direct_info: the coarse solver is not the direct one");
   *info           = glsCoarseDirectInfo{};
   info->requested = mg->coarse_method;
@@ -3136,6 +3205,59 @@ gls_mg_coarse_statistics(glsMG mg, int *n_iterations, int *converged)
     throw std::runtime_error("gls_mg_coarse_statistics: null argument");
   *n_iterations = mg->cg_iters;
   *converged    = mg->cg_conv;
+  GLS_CATCH
+}
+
+glsStatus
+gls_mg_set_coarse_ilu(glsMG mg, const glsILUParams *prm)
+{
+  GLS_TRY
+  if (!mg || !prm)
+    throw std::runtime_error("gls_mg_set_coarse_ilu: null argument");
+  if (prm->fill_level < 0 || !std::isfinite(prm->atol) || !std::isfinite(prm->rtol))
+    throw std::runtime_error("gls_mg_set_coarse_ilu: invalid parameters");
+  if (mg->partitioned)
+    throw std::runtime_error("gls_mg_set_coarse_ilu: the ILU coarse solver is single-domain");
+  if (mg->desc.coarse_amg)
+    throw std::runtime_error("gls_mg_set_coarse_ilu: the coarse solver is the AMG");
+  if (mg->coarse_method != GLS_COARSE_DENSE)
+    throw std::runtime_error("gls_mg_set_coarse_ilu: a direct coarse solver was chosen");
+  if (mg->setup_done)
+    throw std::runtime_error("gls_mg_set_coarse_ilu: call it before gls_mg_setup");
+  mg->coarse_ilu = true;
+  mg->ilu_prm    = *prm;
+  GLS_CATCH
+}
+
+glsStatus
+gls_mg_set_coarse_amg_ilu(glsMG mg, const glsAMGIluParams *prm)
+{
+  GLS_TRY
+  if (!mg || !prm)
+    throw std::runtime_error("gls_mg_set_coarse_amg_ilu: null argument");
+  if (prm->fill_level < 0 || !std::isfinite(prm->atol) || !std::isfinite(prm->rtol))
+    throw std::runtime_error("gls_mg_set_coarse_amg_ilu: invalid parameters");
+  if (!mg->desc.coarse_amg)
+    throw std::runtime_error("gls_mg_set_coarse_amg_ilu: the coarse solver is not the AMG "
+                             "(coarse_amg = 1)");
+  if (mg->partitioned)
+    throw std::runtime_error("gls_mg_set_coarse_amg_ilu: the AMG coarse solver is single-domain");
+  if (mg->setup_done)
+    throw std::runtime_error("gls_mg_set_coarse_amg_ilu: call it before gls_mg_setup");
+  mg->amg_ilu     = prm->smoother_ilu || prm->coarse_ilu;
+  mg->amg_ilu_prm = *prm;
+  GLS_CATCH
+}
+
+glsStatus
+gls_mg_coarse_ilu(glsMG mg, glsILU *ilu, double *setup_ms)
+{
+  GLS_TRY
+  if (!mg || !ilu)
+    throw std::runtime_error("gls_mg_coarse_ilu: null argument");
+  *ilu = mg->ilu;
+  if (setup_ms)
+    *setup_ms = mg->ilu_setup_ms;
   GLS_CATCH
 }
 

@@ -53,7 +53,12 @@ EXPORTS = [
     "gls_op_set_probe_points", "gls_op_probe", "gls_dist_surface_force", "gls_dist_probe",
     "gls_mg_set_coarse_direct", "gls_mg_coarse_direct_info",
     "gls_nd_plan_create", "gls_nd_plan_destroy", "gls_nd_plan_info", "gls_nd_plan_node",
+    "gls_ilu_create", "gls_ilu_refactor", "gls_ilu_destroy", "gls_ilu_vmult", "gls_ilu_info",
+    "gls_ilu_factors", "gls_ilu_host_factor", "gls_amg_create_ilu", "gls_gmres_solve_prec",
+    "gls_mg_set_coarse_ilu", "gls_mg_set_coarse_amg_ilu", "gls_mg_coarse_ilu",
 ]
+
+GLS_PREC_MG, GLS_PREC_ILU, GLS_PREC_AMG = 0, 1, 2
 
 GLS_COARSE_DENSE, GLS_COARSE_ND = 0, 1
 
@@ -125,6 +130,50 @@ class NdPlanNode(C.Structure):
                 ("n_own", C.c_int), ("n_boundary", C.c_int), ("n_cells", C.c_int),
                 ("own", C.POINTER(C.c_int32)), ("boundary", C.POINTER(C.c_int32)),
                 ("map", C.POINTER(C.c_int32)), ("cells", C.POINTER(C.c_int32))]
+
+
+class ILUParams(C.Structure):
+    _fields_ = [("fill_level", C.c_int), ("atol", C.c_double), ("rtol", C.c_double)]
+
+
+class AMGIluParams(C.Structure):
+    _fields_ = [("smoother_ilu", C.c_int), ("coarse_ilu", C.c_int), ("fill_level", C.c_int),
+                ("atol", C.c_double), ("rtol", C.c_double)]
+
+
+def ilu_params(fill_level=0, atol=1e-12, rtol=1.0):
+    """glsILUParams; the defaults are the reference's PreconditionerILU
+    (preconditioner.cc:5-28)"""
+    return ILUParams(int(fill_level), float(atol), float(rtol))
+
+
+def amg_ilu_params(smoother_ilu=True, coarse_ilu=True, fill_level=1, atol=1e-6, rtol=1.0):
+    """glsAMGIluParams; the defaults are the reference's non-default AMG
+    parameters (multigrid.h:52-53, multigrid.cc:403-413)"""
+    return AMGIluParams(int(bool(smoother_ilu)), int(bool(coarse_ilu)), int(fill_level),
+                        float(atol), float(rtol))
+
+
+class ILUInfo(C.Structure):
+    _fields_ = [("n", C.c_int64), ("nnz_a", C.c_int64), ("nnz_l", C.c_int64),
+                ("nnz_u", C.c_int64), ("levels_l", C.c_int), ("levels_u", C.c_int),
+                ("launches_l", C.c_int), ("launches_u", C.c_int), ("max_level_rows", C.c_int),
+                ("group", C.c_int), ("narrow", C.c_int), ("chain", C.c_int),
+                ("min_pivot", C.c_double), ("symbolic_ms", C.c_double),
+                ("numeric_ms", C.c_double), ("upload_ms", C.c_double)]
+
+
+class ILUHostFactor(C.Structure):
+    _fields_ = [("n", C.c_int64), ("nnz_l", C.c_int64), ("nnz_u", C.c_int64),
+                ("levels_l", C.c_int), ("levels_u", C.c_int), ("launches_l", C.c_int),
+                ("launches_u", C.c_int), ("group", C.c_int), ("narrow", C.c_int),
+                ("chain", C.c_int), ("min_pivot", C.c_double),
+                ("l_row_ptr", C.c_void_p), ("l_cols", C.c_void_p), ("u_row_ptr", C.c_void_p),
+                ("u_cols", C.c_void_p), ("l_vals", C.c_void_p), ("u_vals", C.c_void_p),
+                ("row_level_l", C.c_void_p), ("row_level_u", C.c_void_p),
+                ("order_l", C.c_void_p), ("order_u", C.c_void_p),
+                ("launch_l", C.c_void_p), ("launch_u", C.c_void_p),
+                ("solve_dst", C.c_void_p), ("solve_src", C.c_void_p)]
 
 
 class DistDesc(C.Structure):
@@ -250,6 +299,22 @@ def lib():
         L.gls_nd_plan_destroy.restype = None
         L.gls_nd_plan_info.argtypes = [vp, C.POINTER(NdPlanInfo)]
         L.gls_nd_plan_node.argtypes = [vp, C.c_int, C.POINTER(NdPlanNode)]
+        L.gls_ilu_create.argtypes = [i64, vp, vp, vp, C.POINTER(ILUParams), C.POINTER(vp)]
+        L.gls_ilu_refactor.argtypes = [vp, vp]
+        L.gls_ilu_destroy.argtypes = [vp]
+        L.gls_ilu_destroy.restype = None
+        L.gls_ilu_vmult.argtypes = [vp, vp, vp, vp]
+        L.gls_ilu_info.argtypes = [vp, C.POINTER(ILUInfo)]
+        L.gls_ilu_factors.argtypes = [vp, C.c_int, C.POINTER(i64), vp, vp, vp]
+        L.gls_ilu_host_factor.argtypes = [i64, vp, vp, vp, C.POINTER(ILUParams),
+                                          C.POINTER(ILUHostFactor)]
+        L.gls_amg_create_ilu.argtypes = [i64, vp, vp, vp, C.POINTER(AMGParams),
+                                         C.POINTER(AMGIluParams), C.POINTER(vp)]
+        L.gls_gmres_solve_prec.argtypes = [vp, C.c_int, vp, C.POINTER(GMRESDesc), vp, vp,
+                                           C.POINTER(GMRESResult), vp]
+        L.gls_mg_set_coarse_ilu.argtypes = [vp, C.POINTER(ILUParams)]
+        L.gls_mg_set_coarse_amg_ilu.argtypes = [vp, C.POINTER(AMGIluParams)]
+        L.gls_mg_coarse_ilu.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_double)]
         L.gls_last_error.restype = C.c_char_p
         L.gls_timer_enable.argtypes = [C.c_int, C.POINTER(C.c_int)]
         L.gls_timer_reset.argtypes = []
@@ -959,12 +1024,21 @@ def dist_gmres_solve(ops, mgs, xs, bs, n_max_iterations=10000, absolute_toleranc
 class AMG:
     """TrilinosWrappers::PreconditionAMG over the C-ABI (gls_amg_*): built
     from a scipy CSR matrix (initialize), vmult = one V-cycle on device FP64
-    vectors.  The substitute for Trilinos ML (csrc/amg.hip)."""
+    vectors.  The substitute for Trilinos ML (csrc/amg.hip).  smoother_type
+    "ILU" / coarse_type "ILU" (the reference's non-default parameters,
+    multigrid.cc:403-413) replace the Chebyshev smoother / the dense coarsest
+    solve by ILU(ilu_fill) steps; the defaults give the Chebyshev / direct
+    form."""
 
-    def __init__(self, matrix, **params):
+    def __init__(self, matrix, smoother_type="Chebyshev", coarse_type="direct", ilu_fill=1,
+                 ilu_atol=1e-6, ilu_rtol=1.0, **params):
         import torch
         if not torch.cuda.is_available():
             raise GlsError("AMG needs a GPU (no CPU fallback by design)")
+        if smoother_type not in ("Chebyshev", "ILU"):
+            raise ValueError(f"smoother_type: 'Chebyshev' or 'ILU', not {smoother_type!r}")
+        if coarse_type not in ("direct", "ILU"):
+            raise ValueError(f"coarse_type: 'direct' or 'ILU', not {coarse_type!r}")
         A = matrix.tocsr()
         A.sort_indices()
         rp = np.ascontiguousarray(A.indptr, dtype=np.int64)
@@ -972,8 +1046,15 @@ class AMG:
         va = np.ascontiguousarray(A.data, dtype=np.float64)
         self.prm = amg_params(**params)
         h = C.c_void_p()
-        _check(lib().gls_amg_create(A.shape[0], rp.ctypes.data, ci.ctypes.data, va.ctypes.data,
-                                    C.byref(self.prm), C.byref(h)))
+        if smoother_type == "ILU" or coarse_type == "ILU":
+            self.ilu_prm = amg_ilu_params(smoother_type == "ILU", coarse_type == "ILU", ilu_fill,
+                                          ilu_atol, ilu_rtol)
+            _check(lib().gls_amg_create_ilu(A.shape[0], rp.ctypes.data, ci.ctypes.data,
+                                            va.ctypes.data, C.byref(self.prm),
+                                            C.byref(self.ilu_prm), C.byref(h)))
+        else:
+            _check(lib().gls_amg_create(A.shape[0], rp.ctypes.data, ci.ctypes.data,
+                                        va.ctypes.data, C.byref(self.prm), C.byref(h)))
         self.h = h
         self.n = A.shape[0]
 
@@ -1018,6 +1099,120 @@ class AMG:
                 self.h = None
         except Exception:
             pass
+
+
+def _csr_arrays(matrix):
+    """(n, row_ptr, cols, vals) of a scipy matrix as the C ABI takes them
+    (int64 indices, columns ascending per row)"""
+    A = matrix.tocsr()
+    if not A.has_sorted_indices:
+        A = A.sorted_indices()
+    return (A.shape[0], np.ascontiguousarray(A.indptr, dtype=np.int64),
+            np.ascontiguousarray(A.indices, dtype=np.int64),
+            np.ascontiguousarray(A.data, dtype=np.float64))
+
+
+def _ilu_info_of(h):
+    i = ILUInfo()
+    _check(lib().gls_ilu_info(h, C.byref(i)))
+    return {k: getattr(i, k) for k, _ in ILUInfo._fields_}
+
+
+class ILU:
+    """TrilinosWrappers::PreconditionILU over the C-ABI (gls_ilu_*): ILU(k)
+    of a scipy CSR matrix in its own row order, factorised on the host after
+    Ifpack's diagonal modification (atol, rtol); vmult = U^-1 L^-1 on device
+    FP64 vectors (csrc/ilu.hip).  The defaults are the reference's
+    PreconditionerILU (preconditioner.cc:5-28).  GLS_ILU_CHAIN / GLS_ILU_GROUP
+    / GLS_ILU_NARROW are read when the object is created."""
+
+    def __init__(self, matrix, fill_level=0, atol=1e-12, rtol=1.0):
+        import torch
+        if not torch.cuda.is_available():
+            raise GlsError("ILU needs a GPU (no CPU fallback by design)")
+        n, rp, ci, va = _csr_arrays(matrix)
+        self.prm = ILUParams(int(fill_level), float(atol), float(rtol))
+        h = C.c_void_p()
+        _check(lib().gls_ilu_create(n, rp.ctypes.data, ci.ctypes.data, va.ctypes.data,
+                                    C.byref(self.prm), C.byref(h)))
+        self.h, self.n, self.nnz = h, n, va.shape[0]
+
+    def refactor(self, matrix_or_values):
+        """new values on the same pattern: a scipy matrix or its data array"""
+        va = (_csr_arrays(matrix_or_values)[3] if hasattr(matrix_or_values, "tocsr")
+              else np.ascontiguousarray(matrix_or_values, dtype=np.float64))
+        if va.shape[0] != self.nnz:
+            raise GlsError(f"ILU.refactor: {va.shape[0]} values for a pattern of {self.nnz}")
+        _check(lib().gls_ilu_refactor(self.h, va.ctypes.data))
+
+    def vmult(self, dst, src):
+        _check(lib().gls_ilu_vmult(self.h, _vptr(dst), _vptr(src), _stream()))
+        return dst
+
+    def info(self):
+        return _ilu_info_of(self.h)
+
+    def factors(self):
+        """(L, U) as scipy CSR in the original row order: L strictly lower
+        (unit diagonal implied), U with the pivots"""
+        import scipy.sparse as sp
+        out = []
+        for which in (0, 1):
+            nnz = C.c_int64()
+            _check(lib().gls_ilu_factors(self.h, which, C.byref(nnz), None, None, None))
+            rp = np.zeros(self.n + 1, dtype=np.int64)
+            ci = np.zeros(nnz.value, dtype=np.int64)
+            va = np.zeros(nnz.value)
+            _check(lib().gls_ilu_factors(self.h, which, C.byref(nnz), rp.ctypes.data,
+                                         ci.ctypes.data, va.ctypes.data))
+            out.append(sp.csr_matrix((va, ci, rp), shape=(self.n, self.n)))
+        return tuple(out)
+
+    def __del__(self):
+        try:
+            if self.h:
+                lib().gls_ilu_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+
+def ilu_host_factor(matrix, fill_level=0, atol=1e-12, rtol=1.0, solve=None):
+    """gls_ilu_host_factor (host only, no GPU): dict with L, U (scipy CSR as
+    ILU.factors), level_l / level_u (level of each row), order_l / order_u
+    (row at each scheduled position), launch_l / launch_u (rows of first
+    position, end position, first level, end level, chain flag), the counts,
+    and with `solve` the host solve U^-1 L^-1 solve over the schedule."""
+    import scipy.sparse as sp
+    n, rp, ci, va = _csr_arrays(matrix)
+    prm = ILUParams(int(fill_level), float(atol), float(rtol))
+    f = ILUHostFactor()
+    args = (n, rp.ctypes.data, ci.ctypes.data, va.ctypes.data, C.byref(prm), C.byref(f))
+    _check(lib().gls_ilu_host_factor(*args))
+    a = {"l_row_ptr": np.zeros(n + 1, np.int64), "l_cols": np.zeros(f.nnz_l, np.int64),
+         "l_vals": np.zeros(f.nnz_l), "u_row_ptr": np.zeros(n + 1, np.int64),
+         "u_cols": np.zeros(f.nnz_u, np.int64), "u_vals": np.zeros(f.nnz_u),
+         "row_level_l": np.zeros(n, np.int32), "row_level_u": np.zeros(n, np.int32),
+         "order_l": np.zeros(n, np.int32), "order_u": np.zeros(n, np.int32),
+         "launch_l": np.zeros((f.launches_l, 5), np.int32),
+         "launch_u": np.zeros((f.launches_u, 5), np.int32)}
+    if solve is not None:
+        a["solve_src"] = np.ascontiguousarray(solve, dtype=np.float64)
+        a["solve_dst"] = np.zeros(n)
+    for k, v in a.items():
+        setattr(f, k, v.ctypes.data)
+    _check(lib().gls_ilu_host_factor(*args))
+    out = {k: getattr(f, k) for k in ("n", "nnz_l", "nnz_u", "levels_l", "levels_u",
+                                      "launches_l", "launches_u", "group", "narrow", "chain",
+                                      "min_pivot")}
+    out["L"] = sp.csr_matrix((a["l_vals"], a["l_cols"], a["l_row_ptr"]), shape=(n, n))
+    out["U"] = sp.csr_matrix((a["u_vals"], a["u_cols"], a["u_row_ptr"]), shape=(n, n))
+    for k in ("order_l", "order_u", "launch_l", "launch_u"):
+        out[k] = a[k]
+    out["level_l"], out["level_u"] = a["row_level_l"], a["row_level_u"]
+    if solve is not None:
+        out["solve"] = a["solve_dst"]
+    return out
 
 
 class NdPlan:
@@ -1065,7 +1260,8 @@ class Multigrid:
                  smoothing_eig_n_iterations=20, smoothing_range=20.0, coarse_n_iterations=20,
                  outer_precision="f64", compute_evs_n_levels=0, coarse_iterate=False,
                  coarse_reltol=1e-4, coarse_maxiter=10000, coarse_amg=None,
-                 coarse_direct="dense", coarse_leaf_cells=None):
+                 coarse_direct="dense", coarse_leaf_cells=None, coarse_ilu=None,
+                 coarse_amg_ilu=None):
         if coarse_direct not in ("dense", "nd"):
             raise ValueError(f"coarse_direct: 'dense' or 'nd', not {coarse_direct!r}")
         self.ops = list(level_ops)
@@ -1096,6 +1292,27 @@ class Multigrid:
             _check(lib().gls_mg_set_coarse_direct(
                 self.h, GLS_COARSE_ND if coarse_direct == "nd" else GLS_COARSE_DENSE,
                 int(coarse_leaf_cells or 0)))
+        if coarse_ilu is not None:
+            # "gmg coarse grid solver": "ILU": a dict of ilu_params() keywords
+            # or an ILUParams
+            self._coarse_ilu = (coarse_ilu if isinstance(coarse_ilu, ILUParams)
+                                else ilu_params(**coarse_ilu))
+            _check(lib().gls_mg_set_coarse_ilu(self.h, C.byref(self._coarse_ilu)))
+        if coarse_amg_ilu is not None:
+            # the coarse AMG's ILU smoother / coarsest solve: a dict of
+            # amg_ilu_params() keywords or an AMGIluParams
+            self._coarse_amg_ilu = (coarse_amg_ilu if isinstance(coarse_amg_ilu, AMGIluParams)
+                                    else amg_ilu_params(**coarse_amg_ilu))
+            _check(lib().gls_mg_set_coarse_amg_ilu(self.h, C.byref(self._coarse_amg_ilu)))
+
+    def coarse_ilu(self):
+        """(ILU info dict, setup ms) of the coarse ILU (coarse_ilu given), or
+        None before setup."""
+        h, ms = C.c_void_p(), C.c_double()
+        _check(lib().gls_mg_coarse_ilu(self.h, C.byref(h), C.byref(ms)))
+        if not h.value:
+            return None
+        return _ilu_info_of(h), ms.value
 
     def set_coarse_direct(self, coarse_direct, coarse_leaf_cells=None):
         """The direct coarse solver's form ("dense" | "nd"), before setup()."""
@@ -1248,7 +1465,9 @@ class LinearSolverGMRES:
     device-resident gls_gmres_solve: right-preconditioned GMRES with 30
     temporary vectors, tolerance max(relative * |b|, absolute), dst zeroed
     first.  `preconditioner` is a Multigrid (one V-cycle per application,
-    PreconditionerGMG::vmult) or None (identity).  solve() raises GlsError on
+    PreconditionerGMG::vmult), an ILU or an AMG of the operator's system
+    matrix ("preconditioner": "ILU" / "AMG", main.cc:382-395) or None
+    (identity).  solve() raises GlsError on
     no convergence (deal.II's SolverControl::NoConvergence); the statistics of
     the last solve are in .last (n_iterations = SolverControl::last_step())."""
 
@@ -1265,9 +1484,15 @@ class LinearSolverGMRES:
 
     def solve(self, dst, src):
         res = GMRESResult()
-        mg = self.preconditioner.h if self.preconditioner is not None else None
-        rc = lib().gls_gmres_solve(self.op.h, mg, C.byref(self.desc), _vptr(dst), _vptr(src),
-                                   C.byref(res), _stream())
+        p = getattr(self.preconditioner, "preconditioner", self.preconditioner)
+        if isinstance(p, (ILU, AMG)):
+            kind = GLS_PREC_ILU if isinstance(p, ILU) else GLS_PREC_AMG
+            rc = lib().gls_gmres_solve_prec(self.op.h, kind, p.h, C.byref(self.desc), _vptr(dst),
+                                            _vptr(src), C.byref(res), _stream())
+        else:
+            mg = p.h if p is not None else None
+            rc = lib().gls_gmres_solve(self.op.h, mg, C.byref(self.desc), _vptr(dst),
+                                       _vptr(src), C.byref(res), _stream())
         self.last = {f: getattr(res, f) for f, _ in GMRESResult._fields_}
         _check(rc)
         return dst

@@ -411,6 +411,25 @@ class Deck:
         return dict(block_size=self.dim + 1, threshold=1e-14, smoother_sweeps=2,
                     coarse_max_size=2000, elliptic=False, max_levels=10)
 
+    def amg_ilu_parameters(self):
+        """glsAMGIluParams keywords of the deck's coarse AMG: with "gmg coarse
+        grid amg use default parameters" false the reference smooths and
+        solves the coarsest level with ILU (smoother_type = coarse_type =
+        "ILU", level-of-fill 1, atol 1e-6, rtol 1; multigrid.h:52-53,
+        multigrid.cc:403-413); None with the default parameters.  Opt-in:
+        pass it as Multigrid(coarse_amg_ilu=...) beside amg_parameters()."""
+        if self.raw.get("gmg coarse grid amg use default parameters", True):
+            return None
+        return dict(smoother_ilu=True, coarse_ilu=True, fill_level=1, atol=1e-6, rtol=1.0)
+
+    def coarse_ilu_parameters(self):
+        """glsILUParams keywords of "gmg coarse grid solver": "ILU"
+        (multigrid.cc:434-447: PreconditionILU's ILU(0), atol 1e-12, rtol 1),
+        None for any other coarse solver."""
+        if self.coarse_solver != "ILU":
+            return None
+        return dict(fill_level=0, atol=1e-12, rtol=1.0)
+
     @property
     def use_fe_q_iso_q1(self):
         # "gmg coarse grid use fe q iso q1" (main.cc:136, 436-446)

@@ -145,6 +145,40 @@ class GMGPreconditioner:
         return self.mg.vcycle(dst, src)
 
 
+class MatrixPreconditioner:
+    """PreconditionerILU / PreconditionerAMG (preconditioner.cc:5-28, 30-75;
+    "preconditioner": "ILU" | "AMG", main.cc:382-395) on the assembled system
+    matrix of the FP64 operator.  initialize(solution) assembles the matrix at
+    the operator's current linearization point (wire_newton's setup_jacobian
+    has set it, as main.cc does) and factors it: an ILU is created the first
+    time and refactored on its pattern afterwards, an AMG hierarchy is rebuilt.
+    LinearSolverGMRES takes the object as its preconditioner.  params: the
+    keywords of glsamd.ILU / glsamd.AMG (the defaults are ILU(0), atol 1e-12,
+    rtol 1; the AMG defaults with ILU smoother and coarse solver)."""
+
+    def __init__(self, op, kind="ILU", **params):
+        if kind not in ("ILU", "AMG"):
+            raise ValueError(f"kind: 'ILU' or 'AMG', not {kind!r}")
+        self.op, self.kind, self.params = op, kind, dict(params)
+        if kind == "AMG":  # preconditioner.cc:60-61
+            self.params.setdefault("smoother_type", "ILU")
+            self.params.setdefault("coarse_type", "ILU")
+        self.preconditioner = None
+
+    def initialize(self, solution=None):
+        with glsamd.timer_scope("gmg::initialize::" + self.kind.lower()):
+            A = self.op.system_matrix()
+            if self.kind == "ILU" and self.preconditioner is not None:
+                self.preconditioner.refactor(A)
+            elif self.kind == "ILU":
+                self.preconditioner = glsamd.ILU(A, **self.params)
+            else:
+                self.preconditioner = glsamd.AMG(A, **self.params)
+
+    def vmult(self, dst, src):
+        return self.preconditioner.vmult(dst, src)
+
+
 def wire_newton(solver, op, cmask, linear_solver, preconditioner=None):
     """main.cc:805-864: setup_jacobian = set_linearization_point on the fine
     operator; setup_preconditioner = GMG initialize at the solution;

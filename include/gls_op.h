@@ -383,6 +383,22 @@ typedef struct
  * the V-cycle on the current device */
 glsStatus gls_amg_create(int64_t n, const int64_t *row_ptr, const int64_t *cols,
                          const double *vals, const glsAMGParams *prm, glsAMG *out);
+/* The same hierarchy with ILU(k) (the ILU section below) in place of the
+ * Chebyshev smoother and / or the dense coarsest solve: the reference's
+ * non-default AMG parameters smoother_type = coarse_type = "ILU" with
+ * level-of-fill 1, atol 1e-6, rtol 1 (multigrid.h:52-53, multigrid.cc:
+ * 403-413).  smoother_ilu: every smoothed level runs smoother_sweeps steps
+ * x += M^-1 (f - A x), M the ILU of the level matrix (the first pre-smoothing
+ * step starts from zero: x = M^-1 f); coarse_ilu: the coarsest level is
+ * solved by the same steps.  Both 0: exactly gls_amg_create. */
+typedef struct
+{
+  int    smoother_ilu, coarse_ilu, fill_level;
+  double atol, rtol;
+} glsAMGIluParams;
+glsStatus gls_amg_create_ilu(int64_t n, const int64_t *row_ptr, const int64_t *cols,
+                             const double *vals, const glsAMGParams *prm,
+                             const glsAMGIluParams *ilu, glsAMG *out);
 void      gls_amg_destroy(glsAMG amg);
 /* PreconditionAMG::vmult: dst = one V-cycle on src (device FP64 vectors) */
 glsStatus gls_amg_vmult(glsAMG amg, double *dst, const double *src, void *stream);
@@ -396,10 +412,83 @@ glsStatus gls_amg_info(glsAMG amg, int *n_levels, int64_t *sizes, int64_t *nnz,
 glsStatus gls_amg_level_matrix(glsAMG amg, int level, int which, int64_t *n_rows, int64_t *nnz,
                                int32_t *row_ptr, int32_t *cols, double *vals);
 
+/* ------------------------------------------------------------- ILU(k)
+ * TrilinosWrappers::PreconditionILU (Ifpack ILU, one rank: no overlap) on an
+ * assembled CSR matrix: "preconditioner": "ILU" (preconditioner.cc:5-28), the
+ * coarse solver "ILU" (multigrid.cc:434-447) and the AMG's ILU smoother
+ * (multigrid.cc:403-413).  Pattern by the level-of-fill rule in the caller's
+ * row order, row-wise FP64 factorisation on the host after Ifpack's diagonal
+ * modification a_ii <- rtol a_ii + sign(a_ii) atol; the two triangular
+ * solves on the device over a level schedule (csrc/ilu_plan.h, csrc/ilu.hip,
+ * DESIGN.md §4).  A zero or non-finite pivot is an error naming the row. */
+typedef struct glsILU_ *glsILU;
+typedef struct
+{
+  int    fill_level; /* ilu_fill: 0 keeps the pattern of A                  */
+  double atol, rtol; /* ilu_atol, ilu_rtol (PreconditionILU::AdditionalData) */
+} glsILUParams;
+typedef struct
+{
+  int64_t n, nnz_a;
+  int64_t nnz_l, nnz_u;         /* strictly lower entries; upper entries with
+                                   the diagonal                              */
+  int     levels_l, levels_u;   /* dependency levels of the two solves        */
+  int     launches_l, launches_u; /* kernel launches of the two solves        */
+  int     max_level_rows;       /* rows of the largest level                  */
+  int     group, narrow, chain; /* lanes per row, most rows of a level inside
+                                   a chain, chains on (GLS_ILU_GROUP /
+                                   GLS_ILU_NARROW / GLS_ILU_CHAIN, read when
+                                   the factor is created)                    */
+  double  min_pivot;            /* min |u_ii|                                 */
+  double  symbolic_ms, numeric_ms, upload_ms; /* wall ms of the last create or
+                                   refactor (symbolic 0 after a refactor)    */
+} glsILUInfo;
+/* PreconditionILU::initialize: n x n CSR on the host (int64 row_ptr [n + 1],
+ * cols / vals [nnz], columns ascending per row); the factor goes to the
+ * current device */
+glsStatus gls_ilu_create(int64_t n, const int64_t *row_ptr, const int64_t *cols,
+                         const double *vals, const glsILUParams *prm, glsILU *out);
+/* new values on the pattern the factor was created from; after an error
+ * (a zero pivot) the factor refuses vmult until a refactorisation succeeds */
+glsStatus gls_ilu_refactor(glsILU ilu, const double *vals);
+void      gls_ilu_destroy(glsILU ilu);
+/* PreconditionILU::vmult: dst = U^-1 L^-1 src (device FP64 vectors, dst and
+ * src distinct); two applies of one factor are bitwise equal */
+glsStatus gls_ilu_vmult(glsILU ilu, double *dst, const double *src, void *stream);
+glsStatus gls_ilu_info(glsILU ilu, glsILUInfo *info);
+/* the factors in the original row order (which: 0 L, strictly lower, unit
+ * diagonal implied; 1 U with the pivots themselves): nnz, and with non-NULL
+ * arrays the CSR (row_ptr [n + 1], cols / vals [nnz]) */
+glsStatus gls_ilu_factors(glsILU ilu, int which, int64_t *nnz, int64_t *row_ptr, int64_t *cols,
+                          double *vals);
+/* The host plan on its own (no device touched): factors as above, the level
+ * of every row, the scheduled row order and the launches of both solves.
+ * The counts are always written; every array may be NULL (first call: sizes,
+ * second call: contents).  launch_l / launch_u hold 5 ints per launch: first
+ * and end position in the order, first and end level, 1 for a chain (one
+ * workgroup walking its levels) or 0 for a wide level (one grid launch). */
+typedef struct
+{
+  int64_t  n, nnz_l, nnz_u;
+  int      levels_l, levels_u, launches_l, launches_u;
+  int      group, narrow, chain;
+  double   min_pivot;
+  int64_t *l_row_ptr, *l_cols, *u_row_ptr, *u_cols;
+  double  *l_vals, *u_vals;
+  int32_t *row_level_l, *row_level_u; /* [n] level of each row                */
+  int32_t *order_l, *order_u;         /* [n] row at each scheduled position   */
+  int32_t *launch_l, *launch_u;       /* [5 * launches]                       */
+  double  *solve_dst;                 /* [n] U^-1 L^-1 solve_src over the     */
+  const double *solve_src;            /* schedule, or NULL                    */
+} glsILUHostFactor;
+glsStatus gls_ilu_host_factor(int64_t n, const int64_t *row_ptr, const int64_t *cols,
+                              const double *vals, const glsILUParams *prm,
+                              glsILUHostFactor *out);
+
 /* ------------------------------------------------------------ multigrid */
 typedef struct
 {
-  int    n_levels;             /* levels 0 (coarse) .. n_levels-1 (fine)     */
+  int    n_levels;            /* levels 0 (coarse) .. n_levels-1 (fine)     */
   int    smoothing_n_iterations;       /* 5   multigrid.h:31                 */
   int    smoothing_eig_n_iterations;   /* 20  multigrid.h:32                 */
   double smoothing_range;              /* 20  multigrid.h:30                 */
@@ -481,6 +570,20 @@ typedef struct
   double  narrow_ms;      /* the stored (FP32) copies                         */
 } glsCoarseDirectInfo;
 glsStatus gls_mg_coarse_direct_info(glsMG mg, glsCoarseDirectInfo *info);
+/* "gmg coarse grid solver": "ILU" (multigrid.cc:434-447, 472-476, 521-529):
+ * the coarse preconditioner is ILU(k) of the coarse level's assembled system
+ * matrix, applied once (coarse_iterate = 0) or inside the coarse GMRES
+ * (coarse_iterate = 1) on FP64 vectors; coarse_n_iterations is then ignored.
+ * Called before the first setup (an error after it, with coarse_amg = 1,
+ * after a direct solver was chosen, and on partitioned levels).  The first
+ * setup creates the factor, later setups refactor on the same pattern. */
+glsStatus gls_mg_set_coarse_ilu(glsMG mg, const glsILUParams *prm);
+/* the ILU form of the coarse AMG (coarse_amg = 1 needed): every setup builds
+ * the hierarchy with these smoother / coarsest-solve parameters */
+glsStatus gls_mg_set_coarse_amg_ilu(glsMG mg, const glsAMGIluParams *prm);
+/* the ILU of the coarse solver (NULL before the first setup) and the wall ms
+ * of its last setup (system matrix + factorisation + upload) */
+glsStatus gls_mg_coarse_ilu(glsMG mg, glsILU *ilu, double *setup_ms);
 
 /* The nested-dissection plan on its own (host only): the elimination tree
  * over the cells from the cell -> node table, node_dofs[n] dofs of mesh node
@@ -621,6 +724,17 @@ typedef struct
 } glsGMRESResult;
 glsStatus gls_gmres_solve(glsOp op, glsMG mg, const glsGMRESDesc *desc, void *x,
                           const void *b, glsGMRESResult *result, void *stream);
+/* The same solver with the outer preconditioner given by kind ("preconditioner":
+ * "GMG" / "ILU" / "AMG", main.cc:382-395): prec is a glsMG (or NULL: identity;
+ * exactly gls_gmres_solve), a glsILU or a glsAMG built from the operator's
+ * gls_op_system_matrix (its row numbering is the one the solver's device
+ * vectors use).  ILU and AMG are linear maps, so the kept-direction form
+ * applies to them. */
+#define GLS_PREC_MG 0
+#define GLS_PREC_ILU 1
+#define GLS_PREC_AMG 2
+glsStatus gls_gmres_solve_prec(glsOp op, int kind, void *prec, const glsGMRESDesc *desc,
+                               void *x, const void *b, glsGMRESResult *result, void *stream);
 
 /* ---- partitioned multigrid preconditioner and GMRES:
  * PreconditionerGMG::initialize / vmult (multigrid.cc:247-370, 202-220) over

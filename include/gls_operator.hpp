@@ -380,6 +380,23 @@ public:
     return info;
   }
 
+  // "gmg coarse grid solver": "ILU" (multigrid.cc:434-447): ILU(k) of the
+  // coarse level's system matrix as the coarse preconditioner, before the
+  // first initialize()
+  void
+  set_coarse_ilu(const glsILUParams &prm)
+  {
+    check(gls_mg_set_coarse_ilu(h, &prm), "gls_mg_set_coarse_ilu");
+  }
+
+  // the coarse AMG (desc.coarse_amg) with ILU smoothing / an ILU coarsest
+  // solve (multigrid.cc:403-413), before the first initialize()
+  void
+  set_coarse_amg_ilu(const glsAMGIluParams &prm)
+  {
+    check(gls_mg_set_coarse_amg_ilu(h, &prm), "gls_mg_set_coarse_amg_ilu");
+  }
+
   // PreconditionerGMG::initialize (multigrid.cc:247-370)
   void initialize(void *stream = nullptr) { check(gls_mg_setup(h, stream), "gls_mg_setup"); }
 
@@ -410,9 +427,66 @@ private:
   glsMG h = nullptr;
 };
 
+// PreconditionerILU (preconditioner.cc:5-28): ILU(k) of an assembled matrix
+// (Operator::get_system_matrix), factorised on the host, applied on the
+// device to FP64 vectors.  The defaults are the reference's.
+class ILU
+{
+public:
+  ILU() = default;
+  explicit ILU(const Operator::SparseMatrix &A, const glsILUParams &prm = {0, 1e-12, 1.0})
+  {
+    check(gls_ilu_create((int64_t)A.row_ptr.size() - 1, A.row_ptr.data(), A.cols.data(),
+                         A.vals.data(), &prm, &h),
+          "gls_ilu_create");
+  }
+  ~ILU() { gls_ilu_destroy(h); }
+  ILU(const ILU &)            = delete;
+  ILU &operator=(const ILU &) = delete;
+  ILU(ILU &&o) noexcept : h(std::exchange(o.h, nullptr)) {}
+  ILU &
+  operator=(ILU &&o) noexcept
+  {
+    if (this != &o)
+      {
+        gls_ilu_destroy(h);
+        h = std::exchange(o.h, nullptr);
+      }
+    return *this;
+  }
+
+  // new values on the same pattern (the matrix at a new linearisation point)
+  void
+  refactor(const Operator::SparseMatrix &A)
+  {
+    check(gls_ilu_refactor(h, A.vals.data()), "gls_ilu_refactor");
+  }
+
+  // dst = U^-1 L^-1 src (device FP64 vectors, dst != src)
+  void
+  vmult(double *dst, const double *src, void *stream = nullptr) const
+  {
+    check(gls_ilu_vmult(h, dst, src, stream), "gls_ilu_vmult");
+  }
+
+  glsILUInfo
+  info() const
+  {
+    glsILUInfo i;
+    check(gls_ilu_info(h, &i), "gls_ilu_info");
+    return i;
+  }
+
+  glsILU handle() const { return h; }
+
+private:
+  glsILU h = nullptr;
+};
+
 // LinearSolverGMRES (solver_l.h:60-82, solver_l.cc:26-74): right-
 // preconditioned restarted GMRES on the device (gls_gmres_solve), the
-// preconditioner a Multigrid (PreconditionerGMG::vmult, one V-cycle) or none;
+// preconditioner a Multigrid (PreconditionerGMG::vmult, one V-cycle), an ILU
+// of the operator's system matrix ("preconditioner": "ILU") or none;
 // vectors in the operator's layout.  solve() throws gls::Error on no
 // convergence (SolverControl::NoConvergence); last() holds the statistics.
 class LinearSolverGMRES
@@ -424,13 +498,24 @@ public:
     : op(op), mg(preconditioner),
       desc{max_n_tmp_vectors, n_max_iterations, absolute_tolerance, relative_tolerance}
   {}
+  LinearSolverGMRES(const Operator &op, const ILU &preconditioner, int n_max_iterations = 10000,
+                    double absolute_tolerance = 1e-12, double relative_tolerance = 1e-8,
+                    int max_n_tmp_vectors = 30)
+    : op(op), mg(nullptr), ilu(&preconditioner),
+      desc{max_n_tmp_vectors, n_max_iterations, absolute_tolerance, relative_tolerance}
+  {}
 
   void
   solve(void *dst, const void *src, void *stream = nullptr)
   {
-    check(gls_gmres_solve(op.handle(), mg ? mg->handle() : nullptr, &desc, dst, src, &res,
-                          stream),
-          "gls_gmres_solve");
+    if (ilu)
+      check(gls_gmres_solve_prec(op.handle(), GLS_PREC_ILU, ilu->handle(), &desc, dst, src, &res,
+                                 stream),
+            "gls_gmres_solve_prec");
+    else
+      check(gls_gmres_solve(op.handle(), mg ? mg->handle() : nullptr, &desc, dst, src, &res,
+                            stream),
+            "gls_gmres_solve");
   }
 
   const glsGMRESResult &last() const { return res; }
@@ -438,6 +523,7 @@ public:
 private:
   const Operator   &op;
   const Multigrid  *mg;
+  const ILU        *ilu = nullptr;
   glsGMRESDesc      desc;
   glsGMRESResult    res{};
 };
