@@ -90,15 +90,74 @@ slot_class(const ReduceClasses &rc, uint32_t slot)
 // moves 16 B at a quarter of ds_read_b128's rate, MI355X_MICROARCH §LDS).
 // (Pack<T>: common.h)
 
+// What a workgroup needs to know about its brick, one 16-byte record per
+// brick: uniform per workgroup, so it is read by one scalar load
+// (brick_record) and everything derived from it -- the table chunk's and the
+// geometry's base addresses -- stays in scalar registers.
+struct alignas(16) BrickRec
+{
+  uint32_t cell0;  // first cell
+  uint32_t chunk0; // first table chunk
+  uint32_t curved; // 1: per-q geometry for all its cells
+  uint32_t ncell;  // number of cells
+};
+
+// the record of brick `brick` (wave-uniform) through the constant address
+// space: one s_load_dwordx4, no vector memory counter involved
+__device__ __forceinline__ BrickRec
+brick_record(const BrickRec *recs, int brick)
+{
+  typedef uint32_t U4 __attribute__((ext_vector_type(4)));
+  const auto *p = (const __attribute__((address_space(4))) U4 *)(recs + brick);
+  const U4    v = *p;
+  return BrickRec{v[0], v[1], v[2], v[3]};
+}
+
+// the streamed arrays of a brick apply (geometry, tables), copies of the
+// kernel arguments held in scalar registers from the kernel's entry
+// (brick_entry.inc)
+template <typename T>
+struct BrickStreams
+{
+  const T                  *geo_cart, *geo_gen;
+  const typename Pack<T>::V *tab_v;
+  int64_t                   n_cells;
+};
+
+// a load from a wave-uniform base (scalar registers) plus a 32-bit byte
+// offset of the lane: the global_load saddr form, no 64-bit vector address.
+// (The base is device memory by contract: the explicit global address space
+// keeps the load a global_load where the pointer's origin is opaque to the
+// compiler, brick_entry.inc; a flat load would count on both wait counters.)
+template <typename X>
+__device__ __forceinline__ X
+load_so(const X *sbase, uint32_t byte_off)
+{
+  typedef const __attribute__((address_space(1))) char *GC;
+  typedef const __attribute__((address_space(1))) X    *GX;
+  return *(GX)((GC)sbase + byte_off);
+}
+
+// entry i of a small uniform array by selects (values in scalar registers;
+// no per-lane load from the kernel argument segment)
+template <typename T, int n>
+__device__ __forceinline__ T
+select_n(const T (&w)[n], int i)
+{
+  T r = w[0];
+#pragma unroll
+  for (int j = 1; j < n; ++j)
+    r = i == j ? w[j] : r;
+  return r;
+}
+
 template <typename T, int dim, int n>
 struct BrickArgs
 {
   const uint32_t *brick_nodes;  // [n_bricks][L] node | cmask << 28
   const uint32_t *brick_target; // [n_bricks][L] node, or SHARED_BIT | slot
-  const uint32_t *brick_geo; // per brick: bit 0 curved (per-q geometry for all its
-                             // cells) | number of cells << 8
-  const uint32_t *brick_cell0;  // per brick: first cell
-  const uint32_t *brick_chunk0; // per brick: first table chunk
+  const BrickRec *brick_rec;    // per brick (absolute id): first cell, first table
+                                // chunk, geometry type, cells
   const T        *geo_cart;  // [dim+1][cell]               (cells of Cartesian bricks)
   const T        *geo_gen;   // [1+dim^2][plane][cell][line] (cells of curved bricks)
   const typename Pack<T>::V *tab_v; // tables: 16-byte field groups, a chunk per
@@ -142,6 +201,10 @@ struct BrickArgs
   int             td, cw, have_prev, have_old_grad;
   int             det; // deterministic lattice accumulation (GLS_DETERMINISTIC): k_brick<..., DET>
   Shape<T, n>     sh;
+  // the coefficient tables' LDS image (S, S^T, Dq, Dq^T, rows padded to
+  // CoefRow::RP values) in device memory, built once per operator
+  // (coef_image): one load per lane, in flight with the node ids
+  const T        *coef;
 };
 
 // 1D coefficient tables in LDS: S, S^T, Dq, Dq^T, each row padded to whole
@@ -244,6 +307,14 @@ contract_v(const V *in, const T *tab, int pa, int base, int s)
 // critical path.  GLS_TAB_PREFETCH=1 builds it.
 #ifndef GLS_TAB_PREFETCH
 #define GLS_TAB_PREFETCH 0
+#endif
+// Placement of round 0's table and geometry loads in the k_brick prologue
+// (round 7): behind the src gather (default: the staging waits for the
+// gather alone, a counted vmcnt), or ahead of the node-id loads
+// (GLS_TAB_FIRST=1: the staging waits for everything).  Same results; A/B in
+// profiles/r07/prologue/README.md.
+#ifndef GLS_TAB_FIRST
+#define GLS_TAB_FIRST 0
 #endif
 // Non-temporal stores of the brick write-out (dst rows and partial slots;
 // round 6 experiment): the 20 MB an r2 FP64 vmult writes stream out instead of
@@ -441,7 +512,7 @@ group_ut_only(int g, int W)
 // Geometry of a launch's bricks (build_bricks spreads the curved bricks
 // evenly over the XCD runs of each segment): GEO_CART bricks hold
 // one diagonal J^{-1} and det J per cell, GEO_GEN bricks J^{-1} and JxW per
-// q point, GEO_ANY reads the type per brick (brick_geo bit 0).
+// q point, GEO_ANY reads the type per brick (BrickRec::curved).
 enum
 {
   GEO_ANY  = 0,
@@ -465,28 +536,43 @@ struct LaneData
 // loads in flight (no data-dependent branch: the geometry type is per brick,
 // read in the prologue), so the whole set issues back to back and is waited
 // for once, at the q-point physics.
+// Addresses: everything that differs from round to round or from brick to
+// brick is wave-uniform -- the brick's record `rec` (a scalar load), the
+// wavefront's first cell of the round `lc0` (brick-local, a multiple of CPW,
+// in a scalar register) -- and goes into a 64-bit scalar base per stream;
+// the lane adds a 32-bit byte offset made of its cell slot and point only
+// (load_so: the saddr form, no 64-bit vector address arithmetic).  The
+// per-q arrays' plane stride n_cells nq sizeof(T) is part of that offset
+// and stays below 2^32 (checked where the operator is created).
 template <int dim, int k, typename T, int MODE, int GEO>
 __device__ __forceinline__ void
-load_lane(const BrickArgs<T, dim, k + 1> &a, int64_t cell0, int64_t chunk0, int ncell,
-          bool general, int lcell, bool in_wave, int p, const int (&pa)[3],
-          LaneData<dim, T, MODE> &r)
+load_lane(const BrickArgs<T, dim, k + 1> &a, const BrickStreams<T> &ks, const BrickRec &rec,
+          bool general, int lc0, int slot, bool in_wave, int p, LaneData<dim, T, MODE> &r)
 {
   constexpr int  n   = k + 1;
   constexpr int  nq  = ipow(n, dim);
   constexpr int  CPW = 64 / nq > 0 ? 64 / nq : 1;
+  constexpr int  LPC = ipow(n, dim - 1);
   constexpr bool R   = MODE == MODE_RESIDUAL;
   constexpr int  W   = Pack<T>::W;
+  constexpr uint32_t ST = (uint32_t)sizeof(T);
   using V            = typename Pack<T>::V;
   using F            = Fields<dim>;
   constexpr int NG   = (F::N + W - 1) / W;
-  r.active           = in_wave && lcell < ncell;
+  const int ncell    = (int)rec.ncell;
+  r.active           = in_wave && lc0 + slot < ncell;
   // inactive lanes (the 64 % nq left-over lanes, cells past the brick's
-  // end) load the brick's first cell instead of zero-filling ~30 registers
-  // per round: finite values, and JxW = 0 below keeps them out of the sums
-  if (!r.active)
-    lcell = 0;
-  const int64_t cell = cell0 + lcell;
-  const int64_t nqc  = a.n_cells * nq;
+  // end) load a cell of the brick instead of zero-filling ~30 registers per
+  // round -- the first cell of their wavefront's chunk, or the brick's first
+  // chunk when the whole wavefront is past the end (a scalar select): finite
+  // values, and JxW = 0 below keeps them out of the sums
+  const int      lcs   = lc0 < ncell ? lc0 : 0;
+  const uint32_t so    = r.active ? (uint32_t)slot : 0u; // the lane's cell slot in the chunk
+  const int64_t  cell  = (int64_t)rec.cell0 + lcs;       // (uniform) the chunk's first cell
+  const int64_t  nqc   = ks.n_cells * nq;
+  // [field][plane][cell][line] (qindex) relative to `cell`, in bytes
+  const uint32_t oq    = ((uint32_t)(p / LPC) * (uint32_t)ks.n_cells * LPC + so * LPC + p % LPC) * ST;
+  const uint32_t oc    = so * ST; // [field][cell] relative to `cell`
   if (GEO == GEO_CART) // (the Cartesian path reads the diagonal only)
 #pragma unroll
     for (int i = 0; i < dim; ++i)
@@ -508,32 +594,35 @@ load_lane(const BrickArgs<T, dim, k + 1> &a, int64_t cell0, int64_t chunk0, int 
       // their off-diagonal entries (never used) from distinct fixed
       // addresses (identical addresses would be merged into one load and a
       // copy, which waits for it).
-      const int64_t gq = qindex<dim, n>(cell, p, a.n_cells);
-      r.JxW            = *(general ? a.geo_gen + gq : a.geo_cart + dim * a.n_cells + cell);
+      const T *gg = ks.geo_gen + cell * LPC; // (uniform bases; lane offsets oq / oc)
+      const T *gc = ks.geo_cart + cell;
+      r.JxW       = load_so(general ? gg : gc + dim * ks.n_cells, general ? oq : oc);
 #pragma unroll
       for (int i = 0; i < dim; ++i)
 #pragma unroll
         for (int e = 0; e < dim; ++e)
-          r.inv[i][e] = *(general ? a.geo_gen + (1 + i * dim + e) * nqc + gq :
-                          i == e  ? a.geo_cart + i * a.n_cells + cell :
-                                    a.geo_cart + (i * dim + e));
+          r.inv[i][e] = load_so(general ? gg + (1 + i * dim + e) * nqc :
+                                i == e  ? gc + i * ks.n_cells :
+                                          ks.geo_cart + (i * dim + e),
+                                general ? oq : i == e ? oc : 0u);
     }
   else if (GEO == GEO_GEN)
     {
-      const int64_t gq = qindex<dim, n>(cell, p, a.n_cells);
-      r.JxW            = a.geo_gen[gq];
+      const T *gg = ks.geo_gen + cell * LPC;
+      r.JxW       = load_so(gg, oq);
 #pragma unroll
       for (int i = 0; i < dim; ++i)
 #pragma unroll
         for (int e = 0; e < dim; ++e)
-          r.inv[i][e] = a.geo_gen[(1 + i * dim + e) * nqc + gq];
+          r.inv[i][e] = load_so(gg + (1 + i * dim + e) * nqc, oq);
     }
   else
     {
+      const T *gc = ks.geo_cart + cell;
 #pragma unroll
       for (int i = 0; i < dim; ++i)
-        r.inv[i][i] = a.geo_cart[i * a.n_cells + cell];
-      r.JxW = a.geo_cart[dim * a.n_cells + cell];
+        r.inv[i][i] = load_so(gc + i * ks.n_cells, oc);
+      r.JxW = load_so(gc + dim * ks.n_cells, oc);
     }
   // per-q tables (operator_ns.h:120-132): the round's CPW cells form one
   // chunk, each 16-byte field group of it one contiguous wave load; the
@@ -541,7 +630,8 @@ load_lane(const BrickArgs<T, dim, k + 1> &a, int64_t cell0, int64_t chunk0, int 
   // U_t values only is skipped (uniform branch) without the time derivative
   // (other fields a runtime flag switches off are loaded and ignored)
   constexpr int GS = CPW * nq; // group stride in packs
-  const V *tv = a.tab_v + (chunk0 + lcell / CPW) * (NG * GS) + (lcell % CPW) * nq + p;
+  const V       *tv = ks.tab_v + ((int64_t)rec.chunk0 + lcs / CPW) * (NG * GS); // (uniform)
+  const uint32_t ot = (so * nq + (uint32_t)p) * 16u; // the lane's pack in a group
   T        tf[NG * W];
 #pragma unroll
   for (int g = 0; g < NG; ++g)
@@ -552,7 +642,7 @@ load_lane(const BrickArgs<T, dim, k + 1> &a, int64_t cell0, int64_t chunk0, int 
         any = any || field_read<dim, MODE, k>(g * W + w);
       V v = {};
       if (any && (!group_ut_only<dim, MODE, k>(g, W) || a.td))
-        v = tv[g * GS];
+        v = load_so(tv + g * GS, ot);
 #pragma unroll
       for (int w = 0; w < W; ++w)
         tf[g * W + w] = v[w];
@@ -572,15 +662,15 @@ load_lane(const BrickArgs<T, dim, k + 1> &a, int64_t cell0, int64_t chunk0, int 
     r.oldg[i] = 0;
   if (R && a.have_old_grad)
     {
-      const int64_t tq = qindex<dim, n>(cell, p, a.n_cells);
+      const T *og = a.old_grad + cell * LPC;
 #pragma unroll
       for (int i = 0; i < LaneData<dim, T, MODE>::NOLD; ++i)
-        r.oldg[i] = a.old_grad[i * nqc + tq];
+        r.oldg[i] = load_so(og + i * nqc, oq);
     }
   if (a.cw)
     {
-      r.d1 = a.cellwise[cell];
-      r.d2 = a.cellwise[a.n_cells + cell];
+      r.d1 = load_so(a.cellwise + cell, oc);
+      r.d2 = load_so(a.cellwise + ks.n_cells + cell, oc);
     }
   else
     {
@@ -597,9 +687,9 @@ template <int dim, int k, typename T, int MODE>
 __device__ __forceinline__ T
 jxw(const LaneData<dim, T, MODE> &r, bool general, const Shape<T, k + 1> &sh, const int (&pa)[3])
 {
-  T w = sh.w[pa[0]] * sh.w[pa[1]];
+  T w = select_n(sh.w, pa[0]) * select_n(sh.w, pa[1]);
   if (dim == 3)
-    w *= sh.w[pa[2]];
+    w *= select_n(sh.w, pa[2]);
   const T j = general ? r.JxW : r.JxW * w;
   return r.active ? j : T(0);
 }
@@ -655,17 +745,24 @@ struct BrickOcc
 // DET: the deterministic lattice accumulation (GLS_DETERMINISTIC: the cells
 // of a round add in cell order between barriers instead of by LDS atomics;
 // its own instantiation, so the default kernels keep their registers)
+// (The deterministic FP64 4-wave kernels are compiled for 3 waves: at 128
+// VGPRs the scalar bases of the streamed loads spill to vector lanes and
+// those to scratch; the barrier-ordered accumulation is the slow part there.)
 template <int dim, int k, typename T, int MODE, int GEO = GEO_ANY, int ZL = 1, bool DET = false>
-__global__ void __launch_bounds__(BLOCK, (BrickOcc<dim, k, T, MODE, GEO, ZL>::waves))
+__global__ void __launch_bounds__(BLOCK, (DET && sizeof(T) == 8 &&
+                                              BrickOcc<dim, k, T, MODE, GEO, ZL>::four ?
+                                            3 :
+                                            BrickOcc<dim, k, T, MODE, GEO, ZL>::waves))
   k_brick(BrickArgs<T, dim, k + 1> a)
 {
+  // (the 4-wave kernels: measured on them; elsewhere the pinned copies cost
+  // registers -- the deterministic build of the same kernel spills with them)
+  constexpr bool ENTRY_PIN = BrickOcc<dim, k, T, MODE, GEO, ZL>::four && k == 2 && !DET;
+#include "brick_entry.inc"
   if constexpr (GEO == GEO_ANY && BrickOcc<dim, k, T, MODE, GEO, ZL>::four)
     {
       // the round loop compiled once per brick geometry (BrickOcc)
-      const int brick = (int)a.brick_begin + (int)blockIdx.x;
-      if (brick >= (int)a.brick_end)
-        return;
-      if (a.brick_geo[brick] & 1u) // (wave-uniform: per brick)
+      if (rec.curved) // (wave-uniform: per brick)
         {
           constexpr int G = GEO_GEN;
 #include "brick_body.inc"
@@ -735,11 +832,13 @@ template <int dim, int k, typename T, int MODE, int GEO = GEO_ANY, bool DET = fa
 __global__ void __launch_bounds__(BLOCK, 3)
   k_brick_sweeps(BrickArgs<T, dim, k + 1> a, SweepArgs sw)
 {
-  constexpr int ZL = 1;
+  constexpr int  ZL        = 1;
+  constexpr bool ENTRY_PIN = false;
+#include "brick_entry.inc"
   if constexpr (GEO == GEO_ANY && BrickOcc<dim, k, T, MODE, GEO, ZL>::four)
     {
       // one body per brick geometry, as k_brick's (the same arithmetic)
-      if (a.brick_geo[(int)a.brick_begin + (int)blockIdx.x] & 1u)
+      if (rec.curved)
         {
           constexpr int G = GEO_GEN;
 #include "brick_sweeps.inc"

@@ -8,25 +8,36 @@
 // Expects in scope: dim, k, T, MODE, GEO, ZL, DET (template parameters), G, a.
 #include "brick_setup.inc"
 
-  // ---- prologue: every load that does not depend on another is issued
-  // up front (lattice node ids, write-out targets, round 0's geometry and
-  // tables), so the block pays one HBM latency before its first sweep
+  // ---- prologue.  In flight from brick_setup.inc: the brick's record (a
+  // scalar load) and the coefficient image.  Then, back to back with no wait
+  // between them: the lattice node ids and write-out targets, the src gather
+  // (which needs the node ids: the one dependent memory round trip) and round
+  // 0's geometry and tables, whose addresses come from the record alone.  The
+  // staging waits for the gather; round 0's loads stay in flight behind it.
+  // Every lane loads: lanes past the lattice's end read its last entry and
+  // drop it, so no branch surrounds a load and the wait counters stay exact.
+  const bool general = G == GEO_GEN || (G == GEO_ANY && rec.curved != 0);
+  const int  ncell   = (int)rec.ncell;
+  LaneData<dim, T, MODE> cur;
+#if GLS_TAB_FIRST
+  // the other placement (A/B build, brick.h GLS_TAB_FIRST): round 0's loads
+  // ahead of the node ids; the staging then waits for them too
+  if constexpr (!(FOUR && G == GEO_GEN))
+    load_lane<dim, k, T, MODE, G>(a, ks, rec, general, wcell0, slot, in_wave, p, cur);
+#endif
   constexpr int   NI = (BrickLattice<dim, k, ZL>::L + BLOCK - 1) / BLOCK;
-  const uint32_t *bn = a.brick_nodes + brick * (int64_t)L;
-  const uint32_t *bt = a.brick_target + brick * (int64_t)L;
+  const uint32_t *bn = k_nodes + brick * (int64_t)L;
+  const uint32_t *bt = k_target + brick * (int64_t)L;
   uint32_t        pk[NI], tg[NI];
 #pragma unroll
   for (int it = 0; it < NI; ++it)
     {
-      const int i = t + it * BLOCK;
-      pk[it]      = i < L ? bn[i] : 0u;
-      tg[it]      = i < L ? bt[i] : 0u;
+      const int      i  = t + it * BLOCK;
+      const uint32_t ic = (uint32_t)(i < L ? i : L - 1) * 4u;
+      const uint32_t pl = load_so(bn, ic), tl = load_so(bt, ic);
+      pk[it]            = i < L ? pl : 0u;
+      tg[it]            = i < L ? tl : 0u;
     }
-  const uint32_t binfo   = a.brick_geo[brick];
-  const bool     general = G == GEO_GEN || (G == GEO_ANY && (binfo & 1u) != 0);
-  const int      ncell   = (int)(binfo >> 8);
-  const uint32_t cell0   = a.brick_cell0[brick];
-  const uint32_t chunk0  = a.brick_chunk0[brick];
 
   // ---- stage the brick's src values once per node (read_dof_values:
   // homogeneous constraints read as 0; the residual reads plain values).
@@ -41,7 +52,16 @@
     {
       const int      i    = t + it * BLOCK;
       const uint32_t node = pk[it] & NODE_MASK;
-      if (QREC && i < L && node != UNUSED_NODE && a.qslots && (tg[it] & SHARED_BIT))
+      if (!(QREC && a.qslots)) // (uniform)
+        {
+          // branch-free: lanes past the lattice's end and the unused lattice
+          // nodes of a split brick load node 0; the staging drops it (a
+          // select on the loaded value here would be turned into a branch
+          // around the load)
+          const bool used = i < L && node != UNUSED_NODE;
+          load_node<T, nc>(a.src, used ? node : 0u, u[it]);
+        }
+      else if (QREC && i < L && node != UNUSED_NODE && (tg[it] & SHARED_BIT))
         {
           // the previous apply's shared-node reduction of this node, in
           // k_shared_reduce_cls's order and arithmetic (bitwise the same)
@@ -120,12 +140,10 @@
     }
   // round 0's tables and geometry, behind the gather (FOUR: Cartesian bricks
   // only; curved bricks load theirs after the evaluate sweeps)
-  LaneData<dim, T, MODE> cur;
   // (FOUR curved bricks: after the evaluate sweeps; issuing their geometry
   // here instead measured the same, profiles/r05/explore/ab_lattice_pad.txt)
-  if constexpr (!(FOUR && G == GEO_GEN))
-    load_lane<dim, k, T, MODE, G>(a, cell0, chunk0, ncell, general, wave * CPW + slot, in_wave, p,
-                                  pa, cur);
+  if constexpr (!GLS_TAB_FIRST && !(FOUR && G == GEO_GEN))
+    load_lane<dim, k, T, MODE, G>(a, ks, rec, general, wcell0, slot, in_wave, p, cur);
 #if GLS_TAB_PREFETCH
   if constexpr (FOUR && MODE == MODE_NEWTON)
     if (step < ncell)
@@ -137,7 +155,7 @@
         constexpr int NGR   = (F::N + W - 1) / W;
         constexpr int BYTES = F::NEWTON * CPW * nq * (int)sizeof(T);
         const char   *c0 = reinterpret_cast<const char *>(
-          a.tab_v + (int64_t)(chunk0 + step / CPW + wave) * (NGR * CPW * nq));
+          a.tab_v + (int64_t)(rec.chunk0 + step / CPW + wave) * (NGR * CPW * nq));
         const uintptr_t b0 = (uintptr_t)c0 & ~(uintptr_t)127;
         const int       nl = (int)(((uintptr_t)c0 + BYTES - b0 + 127) / 128);
         const char     *pl = reinterpret_cast<const char *>(b0) + 128 * (lane < nl ? lane : nl - 1);
@@ -154,6 +172,9 @@
                      : "m0");
       }
 #endif
+  // the coefficient tables' image to LDS (its load is older than the gather)
+  if (t < NCOEF)
+    s_tab[t] = coef_v;
 #pragma unroll
   for (int it = 0; it < NI; ++it)
     {
@@ -163,10 +184,12 @@
       const int      iz = idiv_f(i, a.rLxy), iy = idiv_f(i - iz * Lxy, a.rLx);
       const int      ip = (i - iz * Lxy - iy * a.Lx) + a.PLx * (iy + a.PLy * iz);
       const uint32_t cm = pk[it] >> 28;
+      // unused lattice nodes of a split brick stage zeros
+      const bool     un = (pk[it] & NODE_MASK) == UNUSED_NODE;
 #pragma unroll
       for (int c = 0; c < nc; ++c)
         {
-          if (!R && ((cm >> c) & 1))
+          if (un || (!R && ((cm >> c) & 1)))
             u[it][c] = T(0);
           s_acc[c * LP + ip] = 0.0;
         }

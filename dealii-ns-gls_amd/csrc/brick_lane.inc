@@ -2,6 +2,9 @@
 // slot, point, sweep buffers (from t; included by brick_setup.inc, and by
 // brick_sweeps.inc inside its sweep loop from an opaque copy of t).
   const int  wave    = t >> 6, lane = t & 63;
+  // the wavefront's first cell slot of a round in a scalar register (the
+  // streamed loads' bases are scalar, brick.h load_lane)
+  const int  wcell0  = __builtin_amdgcn_readfirstlane(wave) * CPW;
   // XD (3D Q2, brick.h xline): lane 16 r + 3 s + x holds point x of x-line
   // 5 r + s (cell (5 r + s) / 9, line (y, z) = its remainder); the 16th lane
   // of every row and lines 18, 19 idle.  Otherwise one lane per (cell, point)

@@ -3,9 +3,18 @@
 // brick_sweeps.inc after the src lattice is staged and round 0's LaneData
 // (cur) is loaded or resident.  Leaves the brick's A src in s_acc.
   // the lane's tensor quadrature weight (Cartesian bricks: JxW = det J w_q)
-  T wq_lane = a.sh.w[pa[0]] * a.sh.w[pa[1]];
+  // (the three 1D weights are scalars of the kernel arguments, picked by
+  // selects: the same values and products as a lookup by pa)
+  // (opaque copies: a select between loads of kernel arguments would be
+  // folded back into one per-lane load from a selected address)
+  static_assert(n <= 4, "1D quadrature weights picked by selects");
+  T w_0 = a.sh.w[0], w_1 = a.sh.w[n > 1 ? 1 : 0], w_2 = a.sh.w[n > 2 ? 2 : 0],
+    w_3 = a.sh.w[n > 3 ? 3 : 0];
+  asm volatile("" : "+s"(w_0), "+s"(w_1), "+s"(w_2), "+s"(w_3));
+  const auto w1d = [&](int i) { return i == 1 ? w_1 : i == 2 ? w_2 : i == 3 ? w_3 : w_0; };
+  T          wq_lane = w1d(pa[0]) * w1d(pa[1]);
   if (dim == 3)
-    wq_lane *= a.sh.w[pa[2]];
+    wq_lane *= w1d(pa[2]);
   // the cell rounds, compiled once per brick geometry G (GEO_CART: diagonal
   // J^{-1} and det J per cell; GEO_GEN: J^{-1} and JxW per q point)
   {
@@ -19,8 +28,7 @@
     for (int base = 0; base < ncell; base += step)
       {
         if (LATE && base > 0)
-          load_lane<dim, k, T, MODE, G>(a, cell0, chunk0, ncell, gen, base + wave * CPW + slot,
-                                        in_wave, p, pa, cur);
+          load_lane<dim, k, T, MODE, G>(a, ks, rec, gen, base + wcell0, slot, in_wave, p, cur);
         const int  lcell = base + wave * CPW + slot;
         const bool act   = in_wave && lcell < ncell;
         // the lane's lattice node this round (inactive lanes: the first cell's)
@@ -143,8 +151,8 @@
           {
             // curved brick: this round's tables and geometry, issued now
             __builtin_amdgcn_sched_barrier(0);
-            load_lane<dim, k, T, MODE, GEO_GEN>(a, cell0, chunk0, ncell, true, lcell, in_wave, p,
-                                                pa, cur);
+            load_lane<dim, k, T, MODE, GEO_GEN>(a, ks, rec, true, base + wcell0, slot, in_wave, p,
+                                                cur);
           }
 
         // ---- q-point physics (do_vmult_cell)
@@ -367,8 +375,7 @@
         const int  li_now     = li;
         const bool active_now = cur.active;
         if (!LATE && !ATUSE && base + step < ncell)
-          load_lane<dim, k, T, MODE, G>(a, cell0, chunk0, ncell, gen, base + step + wave * CPW + slot,
-                                        in_wave, p, pa, cur);
+          load_lane<dim, k, T, MODE, G>(a, ks, rec, gen, base + step + wcell0, slot, in_wave, p, cur);
         wave_sync();
         in  = A;
         out = B;

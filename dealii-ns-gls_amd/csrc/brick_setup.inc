@@ -1,7 +1,8 @@
 // brick_setup.inc — the part of the brick kernels' bodies before the gather:
 // LDS carving, coefficient tables, the lane's cell slot and point (included by
 // brick_body.inc and brick_sweeps.inc).
-// Expects in scope: dim, k, T, MODE, GEO, ZL, DET (template parameters), G, a.
+// Expects in scope: dim, k, T, MODE, GEO, ZL, DET (template parameters), G, a, and
+// what brick_entry.inc defines.
   using LDS          = BrickLDS<dim, k, T>;
   using V            = typename Pack<T>::V;
   constexpr int n    = k + 1;
@@ -17,7 +18,7 @@
   static_assert(nq <= 64, "one cell must fit a wavefront");
 
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int L      = a.L;  // lattice nodes (global order of brick_nodes)
+  const int L      = k_L;  // lattice nodes (global order of brick_nodes)
   const int LP     = a.LP; // padded LDS lattice (bank-conflict-free x sweep)
   V        *s_src  = reinterpret_cast<V *>(smem);   // [NP][LP] brick src values
   V        *s_work = s_src + NP * LP;               // [WPB*CPW][WB]
@@ -41,19 +42,15 @@
   // landing area of the L2 prefetch (GLS_TAB_PREFETCH; never read)
   [[maybe_unused]] unsigned char *s_pf = reinterpret_cast<unsigned char *>(s_org + LDS::ORG);
 
-  const int brick = (int)a.brick_begin + (int)blockIdx.x;
-  if (brick >= (int)a.brick_end)
-    return;
   const int t = threadIdx.x;
-  if (t < n * RP)
-    {
-      const int  r = t / RP, j = t % RP;
-      const bool v = j < n;
-      s_tab[TAB_S * n * RP + t]  = v ? a.sh.S[r][j] : T(0);
-      s_tab[TAB_ST * n * RP + t] = v ? a.sh.S[j][r] : T(0);
-      s_tab[TAB_D * n * RP + t]  = v ? a.sh.Dq[r][j] : T(0);
-      s_tab[TAB_DT * n * RP + t] = v ? a.sh.Dq[j][r] : T(0);
-    }
+  // the coefficient tables' image (one load per lane; every lane loads, the
+  // lanes past the image a clamped entry they drop): issued here, not waited
+  // for before the node ids and targets are requested.  The image goes to
+  // LDS at the staging, below the gather, the oldest load in flight there.
+  // (brick, rec and the k_ copies of kernel arguments: brick_entry.inc)
+  constexpr int NCOEF  = 4 * n * RP;
+  static_assert(NCOEF <= BLOCK, "one coefficient per thread");
+  const T       coef_v = load_so(k_coef, (uint32_t)(t < NCOEF ? t : 0) * (uint32_t)sizeof(T));
   if constexpr (XD)
     if (t < 4 * n * TAPS)
       {

@@ -11,27 +11,31 @@
                 "resident sweeps: FP32 3D smoothing levels");
 
   constexpr int   NI = (BrickLattice<dim, k, ZL>::L + BLOCK - 1) / BLOCK;
-  const uint32_t *bn = a.brick_nodes + brick * (int64_t)L;
-  const uint32_t *bt = a.brick_target + brick * (int64_t)L;
+  const uint32_t *bn = k_nodes + brick * (int64_t)L;
+  const uint32_t *bt = k_target + brick * (int64_t)L;
   uint32_t        pk[NI], tg[NI];
 #pragma unroll
   for (int it = 0; it < NI; ++it)
     {
       const int i = t + it * BLOCK;
-      pk[it]      = i < L ? bn[i] : 0u;
-      tg[it]      = i < L ? bt[i] : 0u;
+      const uint32_t ic = (uint32_t)(i < L ? i : L - 1) * 4u;
+      const uint32_t pl = load_so(bn, ic), tl = load_so(bt, ic);
+      pk[it]            = i < L ? pl : 0u;
+      tg[it]            = i < L ? tl : 0u;
     }
   static_assert(NI == 1, "one lattice node per thread");
   // lattice of at most SWEEP_MAX_L = 128 nodes (gls::brick_sweeps checks):
   // thread t + 128 helps thread t rebuild its shared node (slots 4..7 of an
   // 8..11-fold one)
-  const uint32_t tg_hi = t >= 128 && t - 128 < L ? bt[t - 128] : 0u;
-  const uint32_t binfo   = a.brick_geo[brick];
-  const bool     general = G == GEO_GEN || (G == GEO_ANY && (binfo & 1u) != 0);
-  const int      ncell   = (int)(binfo >> 8);
-  const uint32_t cell0   = a.brick_cell0[brick];
-  const uint32_t chunk0  = a.brick_chunk0[brick];
+  const uint32_t tl_hi = load_so(bt, (uint32_t)(t >= 128 && t - 128 < L ? t - 128 : 0) * 4u);
+  const uint32_t tg_hi = t >= 128 && t - 128 < L ? tl_hi : 0u;
+  const bool     general = G == GEO_GEN || (G == GEO_ANY && rec.curved != 0);
+  const int      ncell   = (int)rec.ncell;
   const int      Lxy     = a.Lx * a.Ly;
+  // the coefficient tables' image to LDS (the first sweep's barrier orders it
+  // before the first read)
+  if (t < NCOEF)
+    s_tab[t] = coef_v;
 
   // the iterate at the lattice nodes (sweep j's src), b and D^{-1} there
   T u[NI][nc], xb[NI][nc], xd[NI][nc];
@@ -221,8 +225,7 @@
       // before the granule wait, or kept across the sweeps, they spill)
       LaneData<dim, T, MODE> cur;
       if constexpr (!(FOUR && G == GEO_GEN)) // (curved 4-wave bodies: after the evaluate sweeps)
-        load_lane<dim, k, T, MODE, G>(a, cell0, chunk0, ncell, general, wave * CPW + slot,
-                                      in_wave, p, pa, cur);
+        load_lane<dim, k, T, MODE, G>(a, ks, rec, general, wcell0, slot, in_wave, p, cur);
       // ---- stage the src lattice (homogeneous constraints read as 0)
 #pragma unroll
       for (int it = 0; it < NI; ++it)

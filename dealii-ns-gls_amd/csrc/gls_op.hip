@@ -479,7 +479,6 @@ build_bricks(glsOp_ *op, const glsOpDesc *d, const char *cell_curved)
   op->n_shared = (int64_t)shared_nodes.size();
   op->brick_cell0 = bcell0;
   op->brick_ncell  = bncell;
-  upload((void **)&op->d_brick_cell0, bcell0);
   upload((void **)&op->d_brick_nodes, bnodes);
   upload((void **)&op->d_brick_target, target);
   upload((void **)&op->d_shared_nodes, shared_nodes);
@@ -559,7 +558,18 @@ build_table_layout(glsOp_ *op)
               (n_chunks + lc / CPW) * NG * gs + (int64_t)(lc % CPW) * nq * W;
           n_chunks += (op->brick_ncell[b] + CPW - 1) / CPW;
         }
-      upload((void **)&op->d_brick_chunk0, chunk0);
+      // the bricks' records (brick.h BrickRec), indexed by the absolute brick id
+      std::vector<gls::BrickRec> rec((size_t)op->n_bricks);
+      for (int64_t b = 0; b < op->n_bricks; ++b)
+        rec[b] = gls::BrickRec{op->brick_cell0[b], chunk0[b], op->brick_curved[b],
+                               op->brick_ncell[b]};
+      upload(&op->d_brick_rec, rec);
+      // the streamed loads address a q point inside its [plane][cell][line]
+      // array by a 32-bit byte offset from the chunk's first cell (load_lane)
+      if ((uint64_t)op->n_cells * (uint64_t)nq * op->tsize() >= (1ull << 32) - (1u << 16))
+        throw std::runtime_error("gls_op_create: too many cells for the brick kernels' 32-bit "
+                                 "lane offsets (cells x q points x sizeof(T) must stay below "
+                                 "2^32)");
     }
   else
     {
@@ -678,6 +688,27 @@ make_shape(const Basis1D &b)
       s.w[q] = (T)b.qw[q];
     }
   return s;
+}
+
+// The brick kernels' 1D coefficient tables exactly as they lie in LDS
+// ([TAB_S | TAB_ST | TAB_D | TAB_DT][row][CoefRow::RP], the values of
+// make_shape, zero padding): uploaded once per operator, so a workgroup
+// fills its LDS tables with one load per lane.
+template <typename T>
+std::vector<T>
+coef_image(const Basis1D &b, int n)
+{
+  const int      W = 16 / (int)sizeof(T), RP = (n + W - 1) / W * W;
+  std::vector<T> img((size_t)4 * n * RP, T(0));
+  for (int r = 0; r < n; ++r)
+    for (int j = 0; j < n; ++j)
+      {
+        img[(TAB_S * n + r) * RP + j]  = (T)b.S[r * n + j];
+        img[(TAB_ST * n + r) * RP + j] = (T)b.S[j * n + r];
+        img[(TAB_D * n + r) * RP + j]  = (T)b.Dq[r * n + j];
+        img[(TAB_DT * n + r) * RP + j] = (T)b.Dq[j * n + r];
+      }
+  return img;
 }
 
 // ------------------------------------------------------------ dispatch
@@ -817,9 +848,8 @@ struct Impl
     BrickArgs<T, dim, n> a;
     a.brick_nodes   = op->d_brick_nodes;
     a.brick_target  = op->d_brick_target;
-    a.brick_geo     = op->d_brick_geo;
-    a.brick_cell0   = op->d_brick_cell0;
-    a.brick_chunk0  = op->d_brick_chunk0;
+    a.brick_rec     = (const BrickRec *)op->d_brick_rec;
+    a.coef          = (const T *)op->d_coef_image;
     a.tab_v         = (const typename Pack<T>::V *)op->d_tab;
     a.geo_cart      = (const T *)op->d_bgeo_cart; // cell-indexed
     a.geo_gen       = (const T *)op->d_bgeo_gen;  // cell-indexed
@@ -1864,8 +1894,8 @@ gls_op_create(const glsOpDesc *d, glsOp *out)
       for (int64_t b = 0; b < op->n_bricks; ++b)
         {
           op->n_curved_bricks += bgeo[b] & 1u;
-          bgeo[b] |= op->brick_ncell[b] << 8;
         }
+      op->brick_curved = bgeo;
       for (int64_t c = 0; c < C; ++c)
         {
           const uint32_t cg = cell_geo[c];
@@ -1898,7 +1928,6 @@ gls_op_create(const glsOpDesc *d, glsOp *out)
                 bgen[(size_t)f * C * nq + host_qindex(dim, n, c, q, C)] = vals[f];
             }
         }
-      upload((void **)&op->d_brick_geo, bgeo);
     }
   if (op->prec == GLS_F64)
     {
@@ -1926,6 +1955,13 @@ gls_op_create(const glsOpDesc *d, glsOp *out)
     }
   const size_t ts = op->tsize();
   build_table_layout(op);
+  if (op->use_brick)
+    {
+      if (op->prec == GLS_F64)
+        upload(&op->d_coef_image, coef_image<double>(op->basis, n));
+      else
+        upload(&op->d_coef_image, coef_image<float>(op->basis, n));
+    }
   HIP_THROW(hipMalloc(&op->d_tab, std::max<size_t>(1, (size_t)op->tab_elems * ts)));
   HIP_THROW(hipMemset(op->d_tab, 0, std::max<size_t>(1, (size_t)op->tab_elems * ts)));
   HIP_THROW(hipMalloc(&op->d_cellwise, std::max<size_t>(1, 2 * (size_t)d->n_cells * ts)));
@@ -1950,7 +1986,7 @@ gls_op_destroy(glsOp op)
                   op->d_hmin,         op->d_tmp,          op->d_cbits,        op->d_brick_nodes,
                   op->d_brick_target, op->d_shared_nodes, op->d_shared_off,
                   op->d_shared_index, op->d_partial,      op->d_bgeo_cart,    op->d_bgeo_gen,
-                  op->d_brick_geo,    op->d_brick_cell0,  op->d_brick_chunk0, op->d_tab_cbase,
+                  op->d_brick_rec,    op->d_coef_image,   op->d_tab_cbase,
                   op->d_node_cmask,   op->d_inhom,        op->gmres_ws,
                   op->d_colour_cells, op->d_sweep_gran[0], op->d_sweep_gran[1],
                   op->d_sweep_err};

@@ -167,9 +167,12 @@ struct glsOp_
   void     *d_partial      = nullptr;
   void     *d_bgeo_cart    = nullptr; // brick path: cell-indexed geometry
   void     *d_bgeo_gen     = nullptr;
-  uint32_t *d_brick_geo    = nullptr; // per brick: curved (bit 0) | cells << 8
-  uint32_t *d_brick_cell0  = nullptr; // per brick: first cell
-  uint32_t *d_brick_chunk0 = nullptr; // per brick: first table chunk
+  // per brick, one 16-byte record (gls::BrickRec: first cell, first table
+  // chunk, curved, cells), read by the brick kernels with one scalar load
+  void     *d_brick_rec    = nullptr;
+  // the brick kernels' coefficient tables as they lie in LDS (S, S^T, Dq,
+  // Dq^T, padded rows; brick.h CoefRow) in the operator's precision
+  void     *d_coef_image   = nullptr;
   // bricks with per-q geometry (any curved cell): none -> the launches run
   // k_brick<GEO_CART>, all -> <GEO_GEN>, some -> <GEO_ANY>
   int64_t   n_curved_bricks = 0;
@@ -179,7 +182,7 @@ struct glsOp_
   std::vector<int64_t> h_tab_cbase; // [n_cells]
   int64_t  *d_tab_cbase = nullptr;
   int64_t   tab_gs = 0, tab_elems = 0;
-  std::vector<uint32_t> brick_cell0, brick_ncell;
+  std::vector<uint32_t> brick_cell0, brick_ncell, brick_curved;
   // resident smoothing sweeps (brick.h k_brick_sweeps; FP32 3D operators with
   // few bricks): two tagged-granule slot buffers ([slot][4] {value, tag}),
   // the waits that hit the spin bound, the last tag used (tags grow across
