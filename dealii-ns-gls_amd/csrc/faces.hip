@@ -577,6 +577,7 @@ gls_op_set_outflow_target(glsOp op, const double *target, void *stream)
       HIP_THROW(hipStreamSynchronize(s));
     }
   HIP_THROW(hipStreamSynchronize(s));
+  gls::op_invalidate_system(op);
   GLS_CATCH
 }
 

@@ -1254,6 +1254,11 @@ op_vmult_device(glsOp op, void *dst, const void *src, hipStream_t s)
 {
   if (!op->have_lin)
     throw std::runtime_error("vmult before set_linearization_point");
+  if (op->matrix_based)
+    {
+      op_csr_vmult_device(op, dst, src, s);
+      return;
+    }
   ApplyFn   af;
   ProduceFn pf;
   select(op, af, pf);
@@ -1998,6 +2003,7 @@ gls_op_destroy(glsOp op)
   if (op->h_sweep_flag)
     (void)hipHostFree(op->h_sweep_flag);
   op->stage.release();
+  gls::system_matrix_release(op);
   gls::faces_release(op);
   gls::forces_release(op);
   delete op;
@@ -2017,6 +2023,7 @@ gls_op_set_parameters(glsOp op, const glsOpParams *prm)
   op->prm      = *prm;
   op->have_prm = true;
   op->version++;
+  gls::op_invalidate_system(op);
   GLS_CATCH
 }
 
@@ -2060,6 +2067,7 @@ gls_op_set_linearization_point(glsOp op, const void *vec, void *stream)
   op->have_lin = true;
   op->t1_valid = false;
   op->version++;
+  gls::op_invalidate_system(op);
   GLS_CATCH
 }
 
@@ -2104,6 +2112,7 @@ gls_op_set_previous_solution(glsOp op, const void *const *hist, int n_hist,
   op->have_prev = true;
   op->t1_valid  = false;
   op->version++;
+  gls::op_invalidate_system(op);
   if (op->prm.theta != 1.0)
     {
       if (!op->d_old_grad)
@@ -2589,6 +2598,7 @@ gls_op_upload_tables(glsOp op, const double *tables, const double *cellwise)
   }
   op->t1_valid = false;
   op->version++;
+  gls::op_invalidate_system(op);
   GLS_CATCH
 }
 

@@ -2817,6 +2817,12 @@ gls_mg_setup(glsMG mg, void *stream)
   if (mg->partitioned)
     throw std::runtime_error("gls_mg_setup: partitioned levels are set up by the host-driven "
                              "distributed multigrid (glsdist.py)");
+  // the fused and resident smoothers run the cell loop: levels stay matrix-free
+  for (size_t l = 0; l < mg->ops.size(); ++l)
+    if (mg->ops[l]->matrix_based)
+      throw std::runtime_error("gls_mg_setup: level " + std::to_string(l) +
+                               " is in matrix-based mode (gls_op_set_matrix_based); level "
+                               "operators stay matrix-free");
   // every allocation and launch of the setup (the AMG hierarchy included)
   // on the levels' device; the caller's current device is restored
   gls::DeviceScope dev(mg->ops[0]->device);

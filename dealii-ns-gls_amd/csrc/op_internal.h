@@ -64,6 +64,10 @@ struct OutflowFaces
 // drag / lift faces and the solution probe (forces.hip): per face the
 // internal cell, the face number and the cell's node coordinates; per probe
 // pair the internal cell and the reference point, grouped by point
+// the assembled system matrix on the device with its assembly plan
+// (assemble.hip)
+struct SystemMatrix;
+
 struct Forces
 {
   bool     have_faces = false, have_points = false; // the matching set_* was called
@@ -134,6 +138,13 @@ struct glsOp_
   gls::VecStage stage; // caller vector layout (host memory / dof permutation)
   gls::OutflowFaces faces; // weak outflow boundary faces (faces.hip)
   gls::Forces forces;      // drag / lift faces and probe points (forces.hip)
+  // the system matrix on the device (assemble.hip): made at the first use,
+  // its values valid until an entry point changes what vmult computes
+  // (op_invalidate_system) or gls_op_invalidate_system; matrix_based: vmult
+  // is the SpMV of that matrix (gls_op_set_matrix_based)
+  gls::SystemMatrix *sysmat       = nullptr;
+  bool               sys_valid    = false;
+  bool               matrix_based = false;
   // gls_gmres_solve workspace (Krylov basis and vectors), grown on demand
   void     *gmres_ws       = nullptr;
   size_t    gmres_ws_bytes = 0;
@@ -344,8 +355,20 @@ void    team_compress_add(glsDist const *m, void *const *v, int n, hipStream_t s
 void    team_allreduce_sum(glsDist const *m, double *const *buf, int64_t count, int n,
                            hipStream_t s);
 
-// the same operator pieces without staging (GMRES, multigrid)
+// the same operator pieces without staging (GMRES, multigrid); in
+// matrix-based mode the SpMV of the system matrix (op_csr_vmult_device)
 void op_vmult_device(glsOp op, void *dst, const void *src, hipStream_t s);
+// every entry point that changes what vmult computes calls this: the device
+// system matrix is assembled again at its next use
+inline void
+op_invalidate_system(glsOp_ *op)
+{
+  op->sys_valid = false;
+}
+// the device system matrix, assembled on s if it is not valid (assemble.hip)
+const SystemMatrix *op_system_matrix_device(glsOp_ *op, hipStream_t s);
+void op_csr_vmult_device(glsOp_ *op, void *dst, const void *src, hipStream_t s);
+void system_matrix_release(glsOp_ *op);
 void op_inverse_diagonal_device(glsOp op, void *diag, hipStream_t s);
 // element matrices of internal cells [b, e) into emat (device, the operator's
 // precision, [cell][col j][row i], local dof = point * (dim+1) + component),

@@ -56,6 +56,8 @@ EXPORTS = [
     "gls_ilu_create", "gls_ilu_refactor", "gls_ilu_destroy", "gls_ilu_vmult", "gls_ilu_info",
     "gls_ilu_factors", "gls_ilu_host_factor", "gls_amg_create_ilu", "gls_gmres_solve_prec",
     "gls_mg_set_coarse_ilu", "gls_mg_set_coarse_amg_ilu", "gls_mg_coarse_ilu",
+    "gls_op_system_matrix_device", "gls_op_invalidate_system", "gls_op_set_matrix_based",
+    "gls_assemble_plan_host",
 ]
 
 GLS_PREC_MG, GLS_PREC_ILU, GLS_PREC_AMG = 0, 1, 2
@@ -139,6 +141,19 @@ class ILUParams(C.Structure):
 class AMGIluParams(C.Structure):
     _fields_ = [("smoother_ilu", C.c_int), ("coarse_ilu", C.c_int), ("fill_level", C.c_int),
                 ("atol", C.c_double), ("rtol", C.c_double)]
+
+
+class DeviceCSR(C.Structure):
+    _fields_ = [("n", C.c_int64), ("nnz", C.c_int64), ("row_ptr", C.c_void_p),
+                ("cols", C.c_void_p), ("vals", C.c_void_p)]
+
+
+class AssemblePlanHost(C.Structure):
+    _fields_ = [("n_dofs", C.c_int64), ("nnz", C.c_int64), ("n_pairs", C.c_int64),
+                ("n_incidence", C.c_int64), ("max_cells_per_node", C.c_int),
+                ("row_ptr", C.c_void_p), ("cols", C.c_void_p), ("pair_ptr", C.c_void_p),
+                ("pair_node", C.c_void_p), ("pair_off", C.c_void_p), ("inc_ptr", C.c_void_p),
+                ("inc_cell", C.c_void_p), ("inc_point", C.c_void_p)]
 
 
 def ilu_params(fill_level=0, atol=1e-12, rtol=1.0):
@@ -265,6 +280,11 @@ def lib():
         L.gls_op_n_outflow_faces.argtypes = [vp, C.POINTER(i64), C.POINTER(C.c_int)]
         L.gls_op_outflow_face_points.argtypes = [vp, vp]
         L.gls_op_set_outflow_target.argtypes = [vp, vp, vp]
+        L.gls_op_system_matrix_device.argtypes = [vp, C.POINTER(DeviceCSR), vp]
+        L.gls_op_invalidate_system.argtypes = [vp]
+        L.gls_op_set_matrix_based.argtypes = [vp, C.c_int]
+        L.gls_assemble_plan_host.argtypes = [C.c_int, C.c_int, i64, i64, vp, vp,
+                                             C.POINTER(AssemblePlanHost)]
         L.gls_op_set_force_faces.argtypes = [vp, i64, vp, vp, vp, C.c_int]
         L.gls_op_surface_force.argtypes = [vp, vp, vp, vp]
         L.gls_op_surface_force_faces.argtypes = [vp, vp, vp, vp]
@@ -428,6 +448,40 @@ def _vptr(v):
         assert v.flags["C_CONTIGUOUS"]
         return C.c_void_p(v.ctypes.data)
     return _ptr(v)
+
+
+class _DeviceArray:
+    """A 1D device array the library owns, through __cuda_array_interface__
+    (torch.as_tensor views it without a copy; torch takes no read-only
+    flag: the callers copy and never write through the view)."""
+
+    def __init__(self, ptr, n, typestr):
+        self.__cuda_array_interface__ = dict(shape=(int(n),), typestr=typestr,
+                                             data=(int(ptr), False), version=2, strides=None)
+
+
+def assemble_plan_host(cell_nodes, cmask, dim, degree, n_nodes=None):
+    """gls_assemble_plan_host (host only, no GPU): dict with the CSR pattern
+    (row_ptr, cols), the node pairs (pair_ptr, pair_node, pair_off) and the
+    node->cell incidence (inc_ptr, inc_cell, inc_point)."""
+    cn = np.ascontiguousarray(cell_nodes, dtype=np.uint32)
+    cm = np.ascontiguousarray(cmask, dtype=np.uint8)
+    n_nodes = len(cm) if n_nodes is None else int(n_nodes)
+    n_cells = cn.shape[0] if cn.ndim == 2 else 0
+    P = AssemblePlanHost()
+    args = (int(dim), int(degree), n_cells, n_nodes, cn.ctypes.data, cm.ctypes.data, C.byref(P))
+    _check(lib().gls_assemble_plan_host(*args))
+    out = dict(row_ptr=np.empty(P.n_dofs + 1, np.int64), cols=np.empty(P.nnz, np.int32),
+               pair_ptr=np.empty(n_nodes + 1, np.int64), pair_node=np.empty(P.n_pairs, np.int32),
+               pair_off=np.empty(P.n_pairs, np.int32), inc_ptr=np.empty(n_nodes + 1, np.int64),
+               inc_cell=np.empty(P.n_incidence, np.int32),
+               inc_point=np.empty(P.n_incidence, np.int32))
+    for k, v in out.items():
+        setattr(P, k, v.ctypes.data)
+    _check(lib().gls_assemble_plan_host(*args))
+    out.update(n_dofs=P.n_dofs, nnz=P.nnz, n_pairs=P.n_pairs, n_incidence=P.n_incidence,
+               max_cells_per_node=P.max_cells_per_node)
+    return out
 
 
 def discover_bricks(mesh_or_cells, dim=None, degree=None):
@@ -656,8 +710,32 @@ class NavierStokesOperator:
 
     def invalidate_system(self):
         """OperatorBase::invalidate_system (operator_ns.cc:229-232): the
-        reference drops its cached system matrix; system_matrix() here is
-        assembled on every call, so there is nothing to drop."""
+        device system matrix is assembled again at its next use
+        (gls_op_invalidate_system; system_matrix() assembles on every call)."""
+        _check(lib().gls_op_invalidate_system(self.h))
+
+    def set_matrix_based(self, on=True):
+        """NavierStokesOperatorMatrixBased (operator_ns.cc:1525-1590, the
+        deck's "use matrix free ns operator": false): vmult is the SpMV of the
+        device system matrix (gls_op_set_matrix_based)."""
+        _check(lib().gls_op_set_matrix_based(self.h, 1 if on else 0))
+
+    def system_matrix_device_raw(self):
+        """gls_op_system_matrix_device: (n, nnz, row_ptr, cols, vals), the
+        last three the operator's own device addresses."""
+        m = DeviceCSR()
+        _check(lib().gls_op_system_matrix_device(self.h, C.byref(m), _stream()))
+        return m.n, m.nnz, m.row_ptr, m.cols, m.vals
+
+    def system_matrix_device(self):
+        """The device system matrix as torch tensors (row_ptr int64, cols
+        int32, vals float64): copies, valid after the next invalidation too."""
+        import torch
+        n, nnz, rp, ci, va = self.system_matrix_device_raw()
+        out = tuple(torch.as_tensor(_DeviceArray(p, cnt, ts), device="cuda").clone()
+                    for p, cnt, ts in ((rp, n + 1, "<i8"), (ci, nnz, "<i4"), (va, nnz, "<f8")))
+        torch.cuda.synchronize()
+        return out
 
     def get_constraints(self):
         """The homogeneous constraints the operator resolves

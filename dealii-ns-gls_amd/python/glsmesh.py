@@ -310,6 +310,7 @@ class Deck:
     cylinder_shift: float = 0.005
     u_max: float = 1.0
     t_init: float = 0.0
+    use_matrix_free_ns_operator: bool = True  # false: NavierStokesOperatorMatrixBased
     outflow_bc: object = None  # override of the deck's outflow switches ("" = none)
     raw: dict = field(default_factory=dict)
 
@@ -554,6 +555,7 @@ def read_deck(path):
     d.cylinder_shift = float(raw.get("simulation geometry cylinder shift", 0.005))
     d.u_max = float(raw.get("simulation u max", 1.0))
     d.t_init = float(raw.get("simulation t init", 0.0))
+    d.use_matrix_free_ns_operator = bool(raw.get("use matrix free ns operator", True))
     return d
 
 

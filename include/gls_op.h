@@ -356,6 +356,66 @@ glsStatus gls_op_element_matrices(glsOp op, double *out);
 glsStatus gls_op_system_matrix(glsOp op, int64_t *nnz, int64_t *row_ptr, int64_t *cols,
                                double *vals);
 
+/* The same matrix kept on the device, and NavierStokesOperatorMatrixBased
+ * (operator_ns.cc:1525-1590; the deck's "use matrix free ns operator":
+ * false), whose vmult is get_system_matrix().vmult().  The pattern (that of
+ * gls_op_system_matrix, int64 row_ptr, int32 cols) and a node->cell incidence
+ * list are planned once per operator on the host; the FP64 values are gathered
+ * on the device from the element matrices, without atomics and in a fixed
+ * order: two assemblies of one state are bitwise equal, whatever the chunk of
+ * cells they work through at a time (256 MB of element matrices, or
+ * GLS_ASSEMBLE_CHUNK_CELLS cells, read at the call).  Single-domain operators
+ * only; too little free device memory is an error.
+ *
+ * gls_op_system_matrix_device assembles on `stream` if the matrix is not
+ * valid and hands out device pointers that belong to the operator: they hold
+ * until the next invalidation or gls_op_destroy.  The matrix becomes invalid
+ * in every call that changes what vmult computes (set_parameters,
+ * set_linearization_point, set_previous_solution, set_outflow_target,
+ * upload_tables) and in gls_op_invalidate_system (invalidate_system /
+ * valid_system, operator_ns.cc:229-232). */
+typedef struct
+{
+  int64_t        n, nnz;
+  const int64_t *row_ptr; /* [n + 1]                          */
+  const int32_t *cols;    /* [nnz] ascending per row          */
+  const double  *vals;    /* [nnz]                            */
+} glsDeviceCSR;
+glsStatus gls_op_system_matrix_device(glsOp op, glsDeviceCSR *out, void *stream);
+glsStatus gls_op_invalidate_system(glsOp op);
+/* on != 0: every vmult of the operator (gls_op_vmult in both vector layouts,
+ * vmult_interface_down, the GMRES solvers) is the SpMV of the device matrix,
+ * assembled lazily on the caller's stream: FP64 values and sums, vectors in
+ * the operator's precision, two applies bitwise equal, dst = src on the
+ * constrained rows.  compute_inverse_diagonal, evaluate_rhs and
+ * evaluate_residual stay matrix-free.  Default 0: nothing changes.  Level
+ * operators of a multigrid stay matrix-free (gls_mg_setup refuses). */
+glsStatus gls_op_set_matrix_based(glsOp op, int on);
+/* The host plan of that assembly on its own (no device, no operator): from
+ * cell_nodes [n_cells][(k+1)^dim] and the nodes' constrained-component bits,
+ * the CSR pattern; the node pairs behind it (pair_ptr [n_nodes + 1]; per
+ * pair the column node and the offset of its first column inside each
+ * unconstrained row of the row node); and the incidence list (inc_ptr
+ * [n_nodes + 1]; per entry the cell and the node's local point, ascending by
+ * cell).  The counts are always written; every array may be NULL (first
+ * call: sizes, second call: contents). */
+typedef struct
+{
+  int64_t  n_dofs, nnz, n_pairs, n_incidence;
+  int      max_cells_per_node;
+  int64_t *row_ptr;   /* [n_dofs + 1]   */
+  int32_t *cols;      /* [nnz]          */
+  int64_t *pair_ptr;  /* [n_nodes + 1]  */
+  int32_t *pair_node; /* [n_pairs]      */
+  int32_t *pair_off;  /* [n_pairs]      */
+  int64_t *inc_ptr;   /* [n_nodes + 1]  */
+  int32_t *inc_cell;  /* [n_incidence]  */
+  int32_t *inc_point; /* [n_incidence]  */
+} glsAssemblePlanHost;
+glsStatus gls_assemble_plan_host(int dim, int degree, int64_t n_cells, int64_t n_nodes,
+                                 const uint32_t *cell_nodes, const uint8_t *node_cmask,
+                                 glsAssemblePlanHost *out);
+
 /* ------------------------------------------------- algebraic multigrid
  * Smoothed-aggregation AMG on an assembled CSR matrix: the substitute for
  * TrilinosWrappers::PreconditionAMG (Trilinos ML) of the coarse solver

@@ -324,6 +324,32 @@ public:
     return A;
   }
 
+  // NavierStokesOperatorMatrixBased (operator_ns.cc:1525-1590): vmult is the
+  // SpMV of the system matrix kept on the device
+  void
+  set_matrix_based(bool on)
+  {
+    check(gls_op_set_matrix_based(h, on ? 1 : 0), "set_matrix_based");
+  }
+
+  // OperatorBase::invalidate_system (operator_ns.cc:229-232): the device
+  // matrix is assembled again at its next use
+  void
+  invalidate_system()
+  {
+    check(gls_op_invalidate_system(h), "invalidate_system");
+  }
+
+  // the device matrix (assembled on stream if invalid); the pointers are the
+  // operator's and hold until the next invalidation
+  glsDeviceCSR
+  system_matrix_device(void *stream = nullptr) const
+  {
+    glsDeviceCSR A{};
+    check(gls_op_system_matrix_device(h, &A, stream), "system_matrix_device");
+    return A;
+  }
+
 private:
   glsOp   h = nullptr;
   int64_t n_force_faces = 0, n_probe_points = 0; // sizes of the lists set above
