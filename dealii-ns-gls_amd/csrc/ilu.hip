@@ -23,9 +23,11 @@
 // entries a row reads, so the work vector is a plain (non-const, non-
 // restrict) pointer read by per-lane vector loads behind the barrier; the
 // read-only factor arrays alone are const __restrict__.
-#include "../../include/gls_op.h"
-#include "common.h"
-#include "ilu_plan.h"
+//
+// The numeric factorisation on the device (gls_ilu_refactor_device,
+// gls_ilu_create_device) is csrc/ilu_factor.hip; the object the two files
+// share is in csrc/ilu_internal.h.
+#include "ilu_internal.h"
 
 #include <chrono>
 #include <cstring>
@@ -94,12 +96,6 @@ __global__ void __launch_bounds__(ILU_CHAIN_THREADS)
       __syncthreads(); // the level's rows are written and visible to the next
     }
 }
-
-struct DevTri
-{
-  int32_t *rp = nullptr, *ci = nullptr, *order = nullptr, *lev_ptr = nullptr;
-  double  *v = nullptr;
-};
 
 template <typename T>
 void
@@ -193,16 +189,6 @@ export_factor(const IluPlan &P, int which, int64_t *nnz, int64_t *row_ptr, int64
 } // namespace
 } // namespace gls
 
-struct glsILU_
-{
-  gls::IluPlan plan;
-  gls::DevTri  L, U;
-  double      *dinv      = nullptr;
-  int          device    = 0;
-  double       upload_ms = 0;
-  bool         valid     = false; // false after a failed refactorisation
-};
-
 namespace gls
 {
 // the internal form of gls_ilu_vmult for the multigrid, the AMG and GMRES
@@ -278,7 +264,8 @@ gls_ilu_refactor(glsILU ilu, const double *vals)
   if (!ilu || !vals)
     throw std::runtime_error("gls_ilu_refactor: null argument");
   DeviceScope ds(ilu->device);
-  ilu->valid = false; // host and device values disagree until the upload below
+  ilu->valid     = false; // host and device values disagree until the upload below
+  ilu->on_device = false;
   ilu_refactor(ilu->plan, vals);
   ilu->plan.symbolic_ms = 0.0;
   // applies in flight on any stream still read the old values
@@ -298,8 +285,87 @@ gls_ilu_destroy(glsILU ilu)
   if (!ilu)
     return;
   gls::free_tri(ilu->L), gls::free_tri(ilu->U);
+  gls::ilu_factor_release(ilu);
   (void)hipFree(ilu->dinv);
   delete ilu;
+}
+
+glsStatus
+gls_ilu_refactor_device(glsILU ilu, const double *d_vals, void *stream)
+{
+  GLS_TRY
+  if (!ilu || !d_vals)
+    throw std::runtime_error("gls_ilu_refactor_device: null argument");
+  gls::DeviceScope ds(ilu->device);
+  gls::ilu_factor_device(ilu, d_vals, (hipStream_t)stream);
+  ilu->plan.symbolic_ms = 0.0;
+  GLS_CATCH
+}
+
+glsStatus
+gls_ilu_create_device(const glsDeviceCSR *A, const glsILUParams *prm, void *stream, glsILU *out)
+{
+  GLS_TRY
+  using namespace gls;
+  if (!A || !prm || !out || !A->row_ptr || !A->cols || !A->vals)
+    throw std::runtime_error("gls_ilu_create_device: null argument");
+  if (A->n <= 0 || A->nnz < 0)
+    throw std::runtime_error("gls_ilu_create_device: empty matrix");
+  IluParams p;
+  p.fill_level = prm->fill_level, p.atol = prm->atol, p.rtol = prm->rtol;
+  hipStream_t st = (hipStream_t)stream;
+  // the pattern to the host, once (the assembly on `stream` comes first)
+  std::vector<int64_t> rp((size_t)A->n + 1), ci((size_t)A->nnz);
+  std::vector<int32_t> ci32((size_t)A->nnz);
+  HIP_THROW(hipMemcpyAsync(rp.data(), A->row_ptr, rp.size() * sizeof(int64_t),
+                           hipMemcpyDeviceToHost, st));
+  if (A->nnz > 0)
+    HIP_THROW(hipMemcpyAsync(ci32.data(), A->cols, ci32.size() * sizeof(int32_t),
+                             hipMemcpyDeviceToHost, st));
+  HIP_THROW(hipStreamSynchronize(st));
+  if (rp[(size_t)A->n] != A->nnz)
+    throw std::runtime_error("gls_ilu_create_device: row_ptr[n] != nnz");
+  std::copy(ci32.begin(), ci32.end(), ci.begin());
+  auto *ilu = new glsILU_();
+  struct Guard
+  {
+    glsILU_ *p;
+    ~Guard()
+    {
+      if (p)
+        gls_ilu_destroy(p);
+    }
+  } guard{ilu};
+  ilu->plan = ilu_make_symbolic(A->n, rp.data(), ci.data(), p, ilu_tuning_from_env());
+  HIP_THROW(hipGetDevice(&ilu->device));
+  upload_tri(ilu->L, ilu->plan.L, false); // the schedule; the values are written on the device
+  upload_tri(ilu->U, ilu->plan.U, false);
+  upload(&ilu->dinv, ilu->plan.dinv);
+  ilu_factor_device(ilu, A->vals, st);
+  guard.p = nullptr;
+  *out    = ilu;
+  GLS_CATCH
+}
+
+glsStatus
+gls_ilu_factor_info(glsILU ilu, glsILUFactorInfo *info)
+{
+  GLS_TRY
+  if (!ilu || !info)
+    throw std::runtime_error("gls_ilu_factor_info: null argument");
+  const gls::IluPlan &P = ilu->plan;
+  std::memset(info, 0, sizeof(*info));
+  info->levels   = (int)P.L.lev_ptr.size() - 1;
+  info->launches = (int)P.factor_launches.size();
+  for (const gls::IluLaunch &q : P.factor_launches)
+    info->chains += q.chain;
+  info->narrow = P.factor_narrow, info->group = P.factor_group, info->rows = P.factor_rows;
+  info->chain       = P.tuning.factor_chain;
+  info->max_row     = P.max_row;
+  info->max_row_limit = gls::ILU_FACTOR_MAX_ROW;
+  info->device      = ilu->on_device ? 1 : 0;
+  info->factor_ms   = ilu->on_device ? ilu->factor_kernels_ms : 0.0;
+  GLS_CATCH
 }
 
 glsStatus
@@ -342,6 +408,11 @@ gls_ilu_factors(glsILU ilu, int which, int64_t *nnz, int64_t *row_ptr, int64_t *
     throw std::runtime_error("gls_ilu_factors: bad argument");
   if (!ilu->valid)
     throw std::runtime_error("gls_ilu_factors: the last refactorisation failed");
+  if (ilu->on_device && vals) // the values of a device factorisation live there
+    {
+      gls::DeviceScope ds(ilu->device);
+      gls::ilu_factor_download(ilu);
+    }
   gls::export_factor(ilu->plan, which, nnz, row_ptr, cols, vals);
   GLS_CATCH
 }
@@ -378,6 +449,40 @@ gls_ilu_host_factor(int64_t n, const int64_t *row_ptr, const int64_t *cols, cons
   launches(out->launch_l, P.L), launches(out->launch_u, P.U);
   if (out->solve_dst && out->solve_src)
     ilu_host_solve(P, out->solve_dst, out->solve_src);
+  GLS_CATCH
+}
+
+glsStatus
+gls_ilu_factor_host(int64_t n, const int64_t *row_ptr, const int64_t *cols, const double *vals,
+                    const glsILUParams *prm, glsILUFactorHost *out)
+{
+  GLS_TRY
+  using namespace gls;
+  if (!prm || !out || !vals)
+    throw std::runtime_error("gls_ilu_factor_host: null argument");
+  IluParams p;
+  p.fill_level = prm->fill_level, p.atol = prm->atol, p.rtol = prm->rtol;
+  IluPlan P = ilu_make_symbolic(n, row_ptr, cols, p, ilu_tuning_from_env());
+  ilu_refactor_scheduled(P, vals);
+  out->n        = P.n;
+  out->levels   = (int)P.L.lev_ptr.size() - 1;
+  out->launches = (int)P.factor_launches.size();
+  out->chains   = 0;
+  for (const IluLaunch &q : P.factor_launches)
+    out->chains += q.chain;
+  out->narrow = P.factor_narrow, out->group = P.factor_group, out->rows = P.factor_rows;
+  out->chain     = P.tuning.factor_chain;
+  out->max_row   = P.max_row;
+  out->min_pivot = P.min_pivot;
+  export_factor(P, 0, &out->nnz_l, out->l_row_ptr, out->l_cols, out->l_vals);
+  export_factor(P, 1, &out->nnz_u, out->u_row_ptr, out->u_cols, out->u_vals);
+  if (out->order && !P.L.order.empty())
+    std::memcpy(out->order, P.L.order.data(), P.L.order.size() * sizeof(int32_t));
+  if (out->row_level && !P.L.level.empty())
+    std::memcpy(out->row_level, P.L.level.data(), P.L.level.size() * sizeof(int32_t));
+  if (int32_t *d = out->launch)
+    for (const IluLaunch &q : P.factor_launches)
+      *d++ = q.pos0, *d++ = q.pos1, *d++ = q.lev0, *d++ = q.lev1, *d++ = q.chain;
   GLS_CATCH
 }
 

@@ -85,15 +85,16 @@ schedule(const IluPlan &P, bool lower, IluTri &T)
 }
 
 void
-plan_launches(IluTri &T, int chain, int narrow)
+plan_launches(const std::vector<int32_t> &lev_ptr, int chain, int narrow,
+              std::vector<IluLaunch> &launches)
 {
-  T.launches.clear();
-  const int32_t n_levels = (int32_t)T.lev_ptr.size() - 1;
+  launches.clear();
+  const int32_t n_levels = (int32_t)lev_ptr.size() - 1;
   for (int32_t l = 0; l < n_levels;)
     {
       IluLaunch q;
-      q.lev0 = l, q.pos0 = T.lev_ptr[(size_t)l];
-      const auto rows = [&](int32_t k) { return T.lev_ptr[(size_t)k + 1] - T.lev_ptr[(size_t)k]; };
+      q.lev0 = l, q.pos0 = lev_ptr[(size_t)l];
+      const auto rows = [&](int32_t k) { return lev_ptr[(size_t)k + 1] - lev_ptr[(size_t)k]; };
       if (chain && rows(l) <= narrow)
         {
           q.chain = 1;
@@ -102,8 +103,8 @@ plan_launches(IluTri &T, int chain, int narrow)
         }
       else
         ++l;
-      q.lev1 = l, q.pos1 = T.lev_ptr[(size_t)l];
-      T.launches.push_back(q);
+      q.lev1 = l, q.pos1 = lev_ptr[(size_t)l];
+      launches.push_back(q);
     }
 }
 } // namespace
@@ -115,6 +116,8 @@ ilu_tuning_from_env()
   t.chain  = env_int("GLS_ILU_CHAIN", 1) != 0;
   t.group  = env_int("GLS_ILU_GROUP", 0);
   t.narrow = env_int("GLS_ILU_NARROW", 0);
+  t.factor_chain  = env_int("GLS_ILU_FACTOR_CHAIN", 1) != 0;
+  t.factor_narrow = env_int("GLS_ILU_FACTOR_NARROW", 0);
   if (t.group != 0 && (t.group > 64 || (t.group & (t.group - 1)) != 0))
     throw std::runtime_error("ilu: GLS_ILU_GROUP must be a power of two in [1, 64]");
   return t;
@@ -124,14 +127,25 @@ IluPlan
 ilu_make_plan(int64_t n, const int64_t *row_ptr, const int64_t *cols, const double *vals,
               const IluParams &prm, const IluTuning &tuning)
 {
-  if (n <= 0 || !row_ptr || !cols || !vals)
+  if (!vals)
+    throw std::runtime_error("ilu: empty matrix or null argument");
+  IluPlan P = ilu_make_symbolic(n, row_ptr, cols, prm, tuning);
+  ilu_refactor(P, vals);
+  return P;
+}
+
+IluPlan
+ilu_make_symbolic(int64_t n, const int64_t *row_ptr, const int64_t *cols, const IluParams &prm,
+                  const IluTuning &tuning)
+{
+  if (n <= 0 || !row_ptr || !cols)
     throw std::runtime_error("ilu: empty matrix or null argument");
   if (n >= (int64_t)0x7fffffff)
     throw std::runtime_error("ilu: n does not fit the 32-bit device indices");
   if (prm.fill_level < 0 || !std::isfinite(prm.atol) || !std::isfinite(prm.rtol))
     throw std::runtime_error("ilu: invalid parameters (fill_level < 0 or non-finite atol / rtol)");
   if (tuning.group < 0 || tuning.group > 64 || (tuning.group & (tuning.group - 1)) != 0 ||
-      tuning.narrow < 0)
+      tuning.narrow < 0 || tuning.factor_narrow < 0)
     throw std::runtime_error("ilu: invalid tuning (group: a power of two in [1, 64])");
   if (row_ptr[0] != 0)
     throw std::runtime_error("ilu: row_ptr[0] != 0");
@@ -215,10 +229,17 @@ ilu_make_plan(int64_t n, const int64_t *row_ptr, const int64_t *cols, const doub
       ;
   P.group  = g;
   P.narrow = tuning.narrow > 0 ? tuning.narrow : ILU_CHAIN_THREADS / g;
-  plan_launches(P.L, tuning.chain, P.narrow);
-  plan_launches(P.U, tuning.chain, P.narrow);
+  plan_launches(P.L.lev_ptr, tuning.chain, P.narrow, P.L.launches);
+  plan_launches(P.U.lev_ptr, tuning.chain, P.narrow, P.U.launches);
+  // ---- the factorisation's launches over the schedule of L
+  for (int64_t i = 0; i < n; ++i)
+    P.max_row = std::max(P.max_row, P.rp[(size_t)i + 1] - P.rp[(size_t)i]);
+  P.factor_group = tuning.group > 0 ? tuning.group : std::min(64, 2 * g);
+  P.factor_rows  = (int)std::max<int64_t>(
+    1, std::min<int64_t>(ILU_CHAIN_THREADS / P.factor_group, ILU_FACTOR_MAX_ROW / P.max_row));
+  P.factor_narrow = tuning.factor_narrow > 0 ? tuning.factor_narrow : P.factor_rows;
+  plan_launches(P.L.lev_ptr, tuning.factor_chain, P.factor_narrow, P.factor_launches);
   P.symbolic_ms = now_ms() - t0;
-  ilu_refactor(P, vals);
   return P;
 }
 
@@ -271,6 +292,81 @@ ilu_refactor(IluPlan &P, const double *vals)
     for (size_t k = 0; k < T->from.size(); ++k)
       T->v[k] = P.val[(size_t)T->from[k]];
   P.numeric_ms = now_ms() - t0;
+}
+
+void
+ilu_refactor_scheduled(IluPlan &P, const double *vals)
+{
+  if (!vals)
+    throw std::runtime_error("ilu: null values");
+  const double  t0 = now_ms();
+  const int64_t n  = P.n;
+  // what k_ilu_load does
+  std::fill(P.val.begin(), P.val.end(), 0.0);
+  for (int64_t k = 0; k < P.nnz_a; ++k)
+    P.val[(size_t)P.a_to_f[(size_t)k]] = vals[k];
+  for (int64_t i = 0; i < n; ++i)
+    {
+      double &d = P.val[(size_t)P.diag[(size_t)i]];
+      d         = P.prm.rtol * d + (d < 0.0 ? -P.prm.atol : P.prm.atol);
+    }
+  // what k_ilu_factor_level / k_ilu_factor_chain do, row by row
+  std::vector<double>  sv((size_t)P.max_row);
+  std::vector<int32_t> sc((size_t)P.max_row);
+  for (const IluLaunch &lq : P.factor_launches)
+    for (int32_t pos = lq.pos0; pos < lq.pos1; ++pos)
+      {
+        const int64_t i   = P.L.order[(size_t)pos];
+        const int64_t r0  = P.rp[(size_t)i];
+        const int32_t len = (int32_t)(P.rp[(size_t)i + 1] - r0);
+        const int32_t nl  = (int32_t)(P.diag[(size_t)i] - r0);
+        for (int32_t e = 0; e < len; ++e)
+          sv[(size_t)e] = P.val[(size_t)(r0 + e)], sc[(size_t)e] = P.ci[(size_t)(r0 + e)];
+        for (int32_t k = 0; k < nl; ++k)
+          {
+            const int64_t p = sc[(size_t)k];
+            const double  l = sv[(size_t)k] / P.val[(size_t)P.diag[(size_t)p]];
+            sv[(size_t)k]   = l;
+            for (int64_t q = P.diag[(size_t)p] + 1; q < P.rp[(size_t)p + 1]; ++q)
+              {
+                const int32_t c  = P.ci[(size_t)q];
+                int32_t       lo = k + 1, hi = len; // the first staged column >= c
+                while (lo < hi)
+                  {
+                    const int32_t mid = lo + (hi - lo) / 2;
+                    if (sc[(size_t)mid] < c)
+                      lo = mid + 1;
+                    else
+                      hi = mid;
+                  }
+                if (lo < len && sc[(size_t)lo] == c)
+                  sv[(size_t)lo] -= l * P.val[(size_t)q];
+              }
+          }
+        for (int32_t e = 0; e < len; ++e)
+          P.val[(size_t)(r0 + e)] = sv[(size_t)e];
+      }
+  // what k_ilu_store does
+  for (IluTri *T : {&P.L, &P.U})
+    for (size_t k = 0; k < T->from.size(); ++k)
+      T->v[k] = P.val[(size_t)T->from[k]];
+  double  min_pivot = HUGE_VAL;
+  int64_t bad       = -1;
+  for (int64_t i = 0; i < n; ++i)
+    {
+      const double piv  = P.val[(size_t)P.diag[(size_t)i]];
+      P.dinv[(size_t)i] = 1.0 / piv;
+      if (piv == 0.0 || !std::isfinite(piv))
+        bad = bad < 0 ? i : bad;
+      else
+        min_pivot = std::min(min_pivot, std::fabs(piv));
+    }
+  P.numeric_ms = now_ms() - t0;
+  if (bad >= 0)
+    throw std::runtime_error("ilu: zero or non-finite pivot in row " + std::to_string(bad) +
+                             " (value " +
+                             std::to_string(P.val[(size_t)P.diag[(size_t)bad]]) + ")");
+  P.min_pivot = min_pivot;
 }
 
 void

@@ -37,6 +37,30 @@
 //                     pass of the chain's workgroup, 1024 / group rows (a
 //                     level of several passes on one CU loses to a grid
 //                     launch: profiles/ilu/README.md)
+//
+// The numeric factorisation on the device (csrc/ilu_factor.hip) runs over the
+// level schedule of L: row i of the IKJ elimination reads exactly the rows of
+// its L pattern.  Its launch plan, IluPlan::factor_launches, has the form of
+// the solves' plans with values of its own:
+//   * lanes per row (factor_group): the row kernel stages the whole row (both
+//     triangles, values and columns) in LDS and strides over the upper part
+//     of one pivot row at a time, so the default is twice the solve's group
+//     (at most 64: a group never spans waves); a forced GLS_ILU_GROUP is
+//     taken as it is.
+//   * rows at once in one workgroup (factor_rows): ILU_CHAIN_THREADS /
+//     factor_group, and no more than fit ILU_FACTOR_LDS_BYTES with
+//     max_row * 12 bytes each (FP64 value + int32 column per entry).  A
+//     pattern whose longest row alone does not fit (max_row >
+//     ILU_FACTOR_MAX_ROW) has no device factorisation.
+//   GLS_ILU_FACTOR_CHAIN=0   every level of the factorisation is a launch of
+//                            its own; default 1
+//   GLS_ILU_FACTOR_NARROW=r  most rows of a level that may join a chain;
+//                            default factor_rows, one pass of the chain's
+//                            workgroup: a row is a serial walk over its L
+//                            entries, each a dependent division and a pass
+//                            over a pivot row, so a second pass doubles the
+//                            level's time while a grid launch spreads the
+//                            same rows over the other compute units
 #pragma once
 
 #include <cstdint>
@@ -46,6 +70,9 @@ namespace gls
 {
 constexpr int ILU_CHAIN_THREADS = 1024; // the chain's single workgroup
 constexpr int ILU_WIDE_THREADS  = 256;  // workgroups of a wide level's grid
+constexpr int ILU_FACTOR_LDS_BYTES = 64 * 1024; // staged rows of one workgroup
+constexpr int ILU_FACTOR_ROW_BYTES = 12;        // per entry: FP64 value, int32 column
+constexpr int ILU_FACTOR_MAX_ROW   = ILU_FACTOR_LDS_BYTES / ILU_FACTOR_ROW_BYTES;
 
 struct IluParams
 {
@@ -58,6 +85,8 @@ struct IluTuning
   int chain  = 1;
   int group  = 0; // 0: from the factor
   int narrow = 0; // 0: from the group
+  int factor_chain  = 1;
+  int factor_narrow = 0; // 0: one pass of the factor chain's workgroup
 };
 IluTuning ilu_tuning_from_env();
 
@@ -100,9 +129,19 @@ struct IluPlan
   double               min_pivot = 0.0;
   IluTri               L, U;
   double               symbolic_ms = 0.0, numeric_ms = 0.0;
+  // the device factorisation: launches over L.order / L.lev_ptr
+  std::vector<IluLaunch> factor_launches;
+  int     factor_group = 0, factor_rows = 0, factor_narrow = 0; // as used
+  int64_t max_row = 0; // entries of the longest row of the pattern
 };
 
-// Symbolic factorisation, schedule and launch plan, then ilu_refactor(vals).
+// Symbolic factorisation, schedule and launch plans; the values are zero
+// until a numeric factorisation.  Throws as ilu_make_plan does, but for the
+// pivots.
+IluPlan ilu_make_symbolic(int64_t n, const int64_t *row_ptr, const int64_t *cols,
+                          const IluParams &prm, const IluTuning &tuning);
+
+// ilu_make_symbolic, then ilu_refactor(vals).
 // Throws std::runtime_error on bad arguments (n <= 0, unsorted or repeated
 // columns, an index out of range, n or the factor's entries >= 2^31) and on
 // a zero or non-finite pivot.
@@ -113,6 +152,17 @@ IluPlan ilu_make_plan(int64_t n, const int64_t *row_ptr, const int64_t *cols, co
 // order of the matrix the plan was made from); refreshes val, dinv, min_pivot
 // and the scheduled copies L.v / U.v
 void ilu_refactor(IluPlan &plan, const double *vals);
+
+// The host emulation of the device factorisation: the scatter of vals onto
+// the zeroed pattern and the diagonal modification, then the rows in the
+// order of factor_launches, each staged (values and columns), eliminated
+// against its L entries in ascending column order with the target of every
+// update found by a binary search beyond the pivot in the staged columns, and
+// written back; then the scheduled copies, the reciprocal pivots and the
+// pivot check (the smallest bad row, which is the one ilu_refactor names: the
+// rows before it do not depend on it).  Every entry sees the operations of
+// ilu_refactor in the same order, so the two are bitwise equal.
+void ilu_refactor_scheduled(IluPlan &plan, const double *vals);
 
 // dst = U^-1 L^-1 src on the host, over the scheduled storage in launch order
 // (what the device does, row by row)

@@ -714,6 +714,7 @@ struct glsMG_
   // preconditioner; created by the first gls_mg_setup, refactored on the
   // same pattern by the later ones.  FP32 levels go through amg_io.
   bool         coarse_ilu = false;
+  bool         coarse_ilu_device = false; // gls_mg_set_coarse_ilu_device
   glsILUParams ilu_prm{};
   glsILU       ilu          = nullptr;
   double       ilu_setup_ms = 0;
@@ -2927,18 +2928,32 @@ gls_mg_setup(glsMG mg, void *stream)
       gls::Section sc("gmg::initialize::ilu", s);
       const auto t0   = std::chrono::steady_clock::now();
       glsOp      op0  = mg->ops[0];
-      int64_t    nnz  = 0;
-      if (gls_op_system_matrix(op0, &nnz, nullptr, nullptr, nullptr) != 0)
-        throw std::runtime_error(std::string("coarse ILU: ") + gls_last_error());
-      std::vector<int64_t> rp((size_t)op0->n_dofs + 1), ci((size_t)nnz);
-      std::vector<double>  va((size_t)nnz);
-      if (gls_op_system_matrix(op0, &nnz, rp.data(), ci.data(), va.data()) != 0)
-        throw std::runtime_error(std::string("coarse ILU: ") + gls_last_error());
-      if (mg->ilu)
-        check_ilu(gls_ilu_refactor(mg->ilu, va.data()));
+      if (mg->coarse_ilu_device)
+        {
+          // assembled and factorised on the device, on the setup stream
+          glsDeviceCSR m{};
+          if (gls_op_system_matrix_device(op0, &m, s) != 0)
+            throw std::runtime_error(std::string("coarse ILU: ") + gls_last_error());
+          if (mg->ilu)
+            check_ilu(gls_ilu_refactor_device(mg->ilu, m.vals, s));
+          else
+            check_ilu(gls_ilu_create_device(&m, &mg->ilu_prm, s, &mg->ilu));
+        }
       else
-        check_ilu(gls_ilu_create(op0->n_dofs, rp.data(), ci.data(), va.data(), &mg->ilu_prm,
-                                 &mg->ilu));
+        {
+          int64_t nnz = 0;
+          if (gls_op_system_matrix(op0, &nnz, nullptr, nullptr, nullptr) != 0)
+            throw std::runtime_error(std::string("coarse ILU: ") + gls_last_error());
+          std::vector<int64_t> rp((size_t)op0->n_dofs + 1), ci((size_t)nnz);
+          std::vector<double>  va((size_t)nnz);
+          if (gls_op_system_matrix(op0, &nnz, rp.data(), ci.data(), va.data()) != 0)
+            throw std::runtime_error(std::string("coarse ILU: ") + gls_last_error());
+          if (mg->ilu)
+            check_ilu(gls_ilu_refactor(mg->ilu, va.data()));
+          else
+            check_ilu(gls_ilu_create(op0->n_dofs, rp.data(), ci.data(), va.data(), &mg->ilu_prm,
+                                     &mg->ilu));
+        }
       if (!mg->amg_io)
         HIP_THROW(hipMalloc((void **)&mg->amg_io, (size_t)2 * op0->n_dofs * 8));
       mg->ilu_setup_ms =
@@ -3232,6 +3247,21 @@ gls_mg_set_coarse_ilu(glsMG mg, const glsILUParams *prm)
     throw std::runtime_error("gls_mg_set_coarse_ilu: call it before gls_mg_setup");
   mg->coarse_ilu = true;
   mg->ilu_prm    = *prm;
+  GLS_CATCH
+}
+
+glsStatus
+gls_mg_set_coarse_ilu_device(glsMG mg, int on)
+{
+  GLS_TRY
+  if (!mg)
+    throw std::runtime_error("gls_mg_set_coarse_ilu_device: null argument");
+  if (!mg->coarse_ilu)
+    throw std::runtime_error("gls_mg_set_coarse_ilu_device: the coarse solver is not the ILU "
+                             "(gls_mg_set_coarse_ilu first)");
+  if (mg->setup_done)
+    throw std::runtime_error("gls_mg_set_coarse_ilu_device: call it before gls_mg_setup");
+  mg->coarse_ilu_device = on != 0;
   GLS_CATCH
 }
 

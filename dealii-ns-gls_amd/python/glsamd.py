@@ -58,6 +58,8 @@ EXPORTS = [
     "gls_mg_set_coarse_ilu", "gls_mg_set_coarse_amg_ilu", "gls_mg_coarse_ilu",
     "gls_op_system_matrix_device", "gls_op_invalidate_system", "gls_op_set_matrix_based",
     "gls_assemble_plan_host",
+    "gls_ilu_refactor_device", "gls_ilu_create_device", "gls_ilu_factor_info",
+    "gls_ilu_factor_host", "gls_mg_set_coarse_ilu_device",
 ]
 
 GLS_PREC_MG, GLS_PREC_ILU, GLS_PREC_AMG = 0, 1, 2
@@ -189,6 +191,23 @@ class ILUHostFactor(C.Structure):
                 ("order_l", C.c_void_p), ("order_u", C.c_void_p),
                 ("launch_l", C.c_void_p), ("launch_u", C.c_void_p),
                 ("solve_dst", C.c_void_p), ("solve_src", C.c_void_p)]
+
+
+class ILUFactorInfo(C.Structure):
+    _fields_ = [("levels", C.c_int), ("launches", C.c_int), ("chains", C.c_int),
+                ("narrow", C.c_int), ("group", C.c_int), ("rows", C.c_int), ("chain", C.c_int),
+                ("device", C.c_int), ("max_row", C.c_int64), ("max_row_limit", C.c_int64),
+                ("factor_ms", C.c_double)]
+
+
+class ILUFactorHost(C.Structure):
+    _fields_ = [("n", C.c_int64), ("nnz_l", C.c_int64), ("nnz_u", C.c_int64),
+                ("max_row", C.c_int64), ("levels", C.c_int), ("launches", C.c_int),
+                ("chains", C.c_int), ("narrow", C.c_int), ("group", C.c_int), ("rows", C.c_int),
+                ("chain", C.c_int), ("min_pivot", C.c_double),
+                ("l_row_ptr", C.c_void_p), ("l_cols", C.c_void_p), ("u_row_ptr", C.c_void_p),
+                ("u_cols", C.c_void_p), ("l_vals", C.c_void_p), ("u_vals", C.c_void_p),
+                ("row_level", C.c_void_p), ("order", C.c_void_p), ("launch", C.c_void_p)]
 
 
 class DistDesc(C.Structure):
@@ -328,6 +347,13 @@ def lib():
         L.gls_ilu_factors.argtypes = [vp, C.c_int, C.POINTER(i64), vp, vp, vp]
         L.gls_ilu_host_factor.argtypes = [i64, vp, vp, vp, C.POINTER(ILUParams),
                                           C.POINTER(ILUHostFactor)]
+        L.gls_ilu_refactor_device.argtypes = [vp, vp, vp]
+        L.gls_ilu_create_device.argtypes = [C.POINTER(DeviceCSR), C.POINTER(ILUParams), vp,
+                                            C.POINTER(vp)]
+        L.gls_ilu_factor_info.argtypes = [vp, C.POINTER(ILUFactorInfo)]
+        L.gls_ilu_factor_host.argtypes = [i64, vp, vp, vp, C.POINTER(ILUParams),
+                                          C.POINTER(ILUFactorHost)]
+        L.gls_mg_set_coarse_ilu_device.argtypes = [vp, C.c_int]
         L.gls_amg_create_ilu.argtypes = [i64, vp, vp, vp, C.POINTER(AMGParams),
                                          C.POINTER(AMGIluParams), C.POINTER(vp)]
         L.gls_gmres_solve_prec.argtypes = [vp, C.c_int, vp, C.POINTER(GMRESDesc), vp, vp,
@@ -1202,7 +1228,13 @@ class ILU:
     Ifpack's diagonal modification (atol, rtol); vmult = U^-1 L^-1 on device
     FP64 vectors (csrc/ilu.hip).  The defaults are the reference's
     PreconditionerILU (preconditioner.cc:5-28).  GLS_ILU_CHAIN / GLS_ILU_GROUP
-    / GLS_ILU_NARROW are read when the object is created."""
+    / GLS_ILU_NARROW are read when the object is created.
+
+    The numeric phase also runs on the device (csrc/ilu_factor.hip, bitwise
+    equal to the host's): refactor_device on a factor made either way,
+    from_operator / refactor_from_operator from the operator's device system
+    matrix; GLS_ILU_FACTOR_CHAIN / GLS_ILU_FACTOR_NARROW are read with the
+    others."""
 
     def __init__(self, matrix, fill_level=0, atol=1e-12, rtol=1.0):
         import torch
@@ -1222,6 +1254,52 @@ class ILU:
         if va.shape[0] != self.nnz:
             raise GlsError(f"ILU.refactor: {va.shape[0]} values for a pattern of {self.nnz}")
         _check(lib().gls_ilu_refactor(self.h, va.ctypes.data))
+
+    @classmethod
+    def from_operator(cls, op, fill_level=0, atol=1e-12, rtol=1.0):
+        """gls_ilu_create_device on the operator's device system matrix
+        (assembled on the current stream if it is not valid): the pattern goes
+        to the host once for the symbolic phase, the values stay on the device"""
+        self = cls.__new__(cls)
+        self.h = None
+        self.prm = ILUParams(int(fill_level), float(atol), float(rtol))
+        n, nnz, rp, ci, va = op.system_matrix_device_raw()
+        m = DeviceCSR(n, nnz, rp, ci, va)
+        h = C.c_void_p()
+        _check(lib().gls_ilu_create_device(C.byref(m), C.byref(self.prm), _stream(), C.byref(h)))
+        self.h, self.n, self.nnz = h, n, nnz
+        return self
+
+    def refactor_from_operator(self, op):
+        """gls_ilu_refactor_device with the operator's device system matrix at
+        its current state (the pattern this factor was made from)"""
+        n, nnz, _, _, va = op.system_matrix_device_raw()
+        if n != self.n or nnz != self.nnz:
+            raise GlsError(f"ILU.refactor_from_operator: a matrix of {n} rows and {nnz} entries "
+                           f"for a pattern of {self.n} and {self.nnz}")
+        _check(lib().gls_ilu_refactor_device(self.h, C.c_void_p(va), _stream()))
+
+    def refactor_device(self, values):
+        """new values on the same pattern from a float64 CUDA tensor (the
+        order of the matrix's data array); the factorisation runs on the
+        device, on the current stream"""
+        import torch
+        if not (isinstance(values, torch.Tensor) and values.is_cuda
+                and values.dtype == torch.float64):
+            raise GlsError("ILU.refactor_device: values must be a float64 CUDA tensor")
+        if values.dim() != 1 or values.shape[0] != self.nnz:
+            raise GlsError(f"ILU.refactor_device: {tuple(values.shape)} values for a pattern "
+                           f"of {self.nnz}")
+        values = values.contiguous()
+        _check(lib().gls_ilu_refactor_device(self.h, _ptr(values), _stream()))
+
+    def factor_info(self):
+        """glsILUFactorInfo as a dict: levels, launches, chains, narrow, group,
+        rows, chain, device (the last factorisation ran there), max_row,
+        max_row_limit, factor_ms"""
+        i = ILUFactorInfo()
+        _check(lib().gls_ilu_factor_info(self.h, C.byref(i)))
+        return {k: getattr(i, k) for k, _ in ILUFactorInfo._fields_}
 
     def vmult(self, dst, src):
         _check(lib().gls_ilu_vmult(self.h, _vptr(dst), _vptr(src), _stream()))
@@ -1290,6 +1368,33 @@ def ilu_host_factor(matrix, fill_level=0, atol=1e-12, rtol=1.0, solve=None):
     out["level_l"], out["level_u"] = a["row_level_l"], a["row_level_u"]
     if solve is not None:
         out["solve"] = a["solve_dst"]
+    return out
+
+
+def ilu_factor_host(matrix, fill_level=0, atol=1e-12, rtol=1.0):
+    """gls_ilu_factor_host (host only, no GPU): the emulation of the device
+    factorisation.  dict with L, U (as ilu_host_factor, bitwise equal to it),
+    level / order of L's schedule, launch (rows of first position, end
+    position, first level, end level, chain flag) and the counts."""
+    import scipy.sparse as sp
+    n, rp, ci, va = _csr_arrays(matrix)
+    prm = ILUParams(int(fill_level), float(atol), float(rtol))
+    f = ILUFactorHost()
+    args = (n, rp.ctypes.data, ci.ctypes.data, va.ctypes.data, C.byref(prm), C.byref(f))
+    _check(lib().gls_ilu_factor_host(*args))
+    a = {"l_row_ptr": np.zeros(n + 1, np.int64), "l_cols": np.zeros(f.nnz_l, np.int64),
+         "l_vals": np.zeros(f.nnz_l), "u_row_ptr": np.zeros(n + 1, np.int64),
+         "u_cols": np.zeros(f.nnz_u, np.int64), "u_vals": np.zeros(f.nnz_u),
+         "row_level": np.zeros(n, np.int32), "order": np.zeros(n, np.int32),
+         "launch": np.zeros((f.launches, 5), np.int32)}
+    for k, v in a.items():
+        setattr(f, k, v.ctypes.data)
+    _check(lib().gls_ilu_factor_host(*args))
+    out = {k: getattr(f, k) for k in ("n", "nnz_l", "nnz_u", "max_row", "levels", "launches",
+                                      "chains", "narrow", "group", "rows", "chain", "min_pivot")}
+    out["L"] = sp.csr_matrix((a["l_vals"], a["l_cols"], a["l_row_ptr"]), shape=(n, n))
+    out["U"] = sp.csr_matrix((a["u_vals"], a["u_cols"], a["u_row_ptr"]), shape=(n, n))
+    out["level"], out["order"], out["launch"] = a["row_level"], a["order"], a["launch"]
     return out
 
 
@@ -1372,10 +1477,18 @@ class Multigrid:
                 int(coarse_leaf_cells or 0)))
         if coarse_ilu is not None:
             # "gmg coarse grid solver": "ILU": a dict of ilu_params() keywords
-            # or an ILUParams
-            self._coarse_ilu = (coarse_ilu if isinstance(coarse_ilu, ILUParams)
-                                else ilu_params(**coarse_ilu))
+            # or an ILUParams; the dict's device=True also turns on
+            # gls_mg_set_coarse_ilu_device (assembly and factorisation on the
+            # device)
+            device = False
+            if not isinstance(coarse_ilu, ILUParams):
+                coarse_ilu = dict(coarse_ilu)
+                device = bool(coarse_ilu.pop("device", False))
+                coarse_ilu = ilu_params(**coarse_ilu)
+            self._coarse_ilu = coarse_ilu
             _check(lib().gls_mg_set_coarse_ilu(self.h, C.byref(self._coarse_ilu)))
+            if device:
+                _check(lib().gls_mg_set_coarse_ilu_device(self.h, 1))
         if coarse_amg_ilu is not None:
             # the coarse AMG's ILU smoother / coarsest solve: a dict of
             # amg_ilu_params() keywords or an AMGIluParams

@@ -154,12 +154,17 @@ class MatrixPreconditioner:
     time and refactored on its pattern afterwards, an AMG hierarchy is rebuilt.
     LinearSolverGMRES takes the object as its preconditioner.  params: the
     keywords of glsamd.ILU / glsamd.AMG (the defaults are ILU(0), atol 1e-12,
-    rtol 1; the AMG defaults with ILU smoother and coarse solver)."""
+    rtol 1; the AMG defaults with ILU smoother and coarse solver).
+    device=True (ILU only): initialize never assembles on the host; the
+    operator's device system matrix is factorised on the device
+    (glsamd.ILU.from_operator, then refactor_from_operator)."""
 
-    def __init__(self, op, kind="ILU", **params):
+    def __init__(self, op, kind="ILU", device=False, **params):
         if kind not in ("ILU", "AMG"):
             raise ValueError(f"kind: 'ILU' or 'AMG', not {kind!r}")
-        self.op, self.kind, self.params = op, kind, dict(params)
+        if device and kind != "ILU":
+            raise ValueError("device=True: the ILU only")
+        self.op, self.kind, self.params, self.device = op, kind, dict(params), bool(device)
         if kind == "AMG":  # preconditioner.cc:60-61
             self.params.setdefault("smoother_type", "ILU")
             self.params.setdefault("coarse_type", "ILU")
@@ -167,6 +172,12 @@ class MatrixPreconditioner:
 
     def initialize(self, solution=None):
         with glsamd.timer_scope("gmg::initialize::" + self.kind.lower()):
+            if self.device:
+                if self.preconditioner is not None:
+                    self.preconditioner.refactor_from_operator(self.op)
+                else:
+                    self.preconditioner = glsamd.ILU.from_operator(self.op, **self.params)
+                return
             A = self.op.system_matrix()
             if self.kind == "ILU" and self.preconditioner is not None:
                 self.preconditioner.refactor(A)

@@ -545,6 +545,68 @@ glsStatus gls_ilu_host_factor(int64_t n, const int64_t *row_ptr, const int64_t *
                               const double *vals, const glsILUParams *prm,
                               glsILUHostFactor *out);
 
+/* The numeric factorisation on the device (csrc/ilu_factor.hip, DESIGN.md
+ * §4): the same row-wise elimination over the level schedule of L, one group
+ * of lanes per row, without FMA contraction, so the factor equals the host's
+ * bit for bit.  The symbolic phase stays on the host.
+ *
+ * gls_ilu_refactor_device: d_vals is a device array of nnz_a FP64 values in
+ * the order of the matrix the factor was created from (by gls_ilu_create or
+ * gls_ilu_create_device; the device copy of the pattern is made at the first
+ * call).  The kernels are enqueued on `stream`, which is synchronised once at
+ * the end to read the status: applies enqueued earlier on the same stream are
+ * ordered before the new values, applies on other streams are the caller's to
+ * order.  A bad pivot is the host's error ("zero or non-finite pivot in row
+ * r", the smallest such row); the factor then refuses vmult until a
+ * refactorisation succeeds, by either path.  A pattern whose longest row
+ * exceeds what the row kernel stages is refused (the message gives both
+ * numbers); the host path remains.
+ * gls_ilu_create_device: the pattern of A (gls_op_system_matrix_device) is
+ * copied to the host once for the symbolic phase, the numeric phase runs on
+ * the device.
+ * After a device factorisation gls_ilu_factors downloads the values,
+ * gls_ilu_info reports min_pivot from the device, numeric_ms is the event time
+ * of the device factorisation and upload_ms is 0. */
+glsStatus gls_ilu_refactor_device(glsILU ilu, const double *d_vals, void *stream);
+glsStatus gls_ilu_create_device(const glsDeviceCSR *A, const glsILUParams *prm, void *stream,
+                                glsILU *out);
+typedef struct
+{
+  int     levels;        /* dependency levels of the factorisation (those of L) */
+  int     launches;      /* kernel launches of the row phase                    */
+  int     chains;        /* of which one-workgroup chains                       */
+  int     narrow;        /* most rows of a level inside a chain
+                            (GLS_ILU_FACTOR_NARROW)                             */
+  int     group;         /* lanes per row                                       */
+  int     rows;          /* rows one workgroup of a chain holds at once         */
+  int     chain;         /* chains on (GLS_ILU_FACTOR_CHAIN)                    */
+  int     device;        /* 1: the last factorisation ran on the device         */
+  int64_t max_row;       /* entries of the longest row of the pattern           */
+  int64_t max_row_limit; /* what the row kernel stages                          */
+  double  factor_ms;     /* device event ms of the row kernels alone in the
+                            last device factorisation (numeric_ms of
+                            glsILUInfo holds load + rows + store)               */
+} glsILUFactorInfo;
+glsStatus gls_ilu_factor_info(glsILU ilu, glsILUFactorInfo *info);
+/* The host emulation of the device factorisation (no device touched): the
+ * rows in factor-launch order, each by the row kernel's procedure.  L / U as
+ * gls_ilu_host_factor gives them (bitwise equal to it), order / row_level of
+ * L's schedule and 5 ints per launch as there.  The counts are always written;
+ * every array may be NULL. */
+typedef struct
+{
+  int64_t  n, nnz_l, nnz_u, max_row;
+  int      levels, launches, chains, narrow, group, rows, chain;
+  double   min_pivot;
+  int64_t *l_row_ptr, *l_cols, *u_row_ptr, *u_cols;
+  double  *l_vals, *u_vals;
+  int32_t *row_level, *order; /* [n]            */
+  int32_t *launch;            /* [5 * launches] */
+} glsILUFactorHost;
+glsStatus gls_ilu_factor_host(int64_t n, const int64_t *row_ptr, const int64_t *cols,
+                              const double *vals, const glsILUParams *prm,
+                              glsILUFactorHost *out);
+
 /* ------------------------------------------------------------ multigrid */
 typedef struct
 {
@@ -638,6 +700,14 @@ glsStatus gls_mg_coarse_direct_info(glsMG mg, glsCoarseDirectInfo *info);
  * after a direct solver was chosen, and on partitioned levels).  The first
  * setup creates the factor, later setups refactor on the same pattern. */
 glsStatus gls_mg_set_coarse_ilu(glsMG mg, const glsILUParams *prm);
+/* on != 0: the setups take gls_op_system_matrix_device of the coarse operator
+ * on the setup stream, gls_ilu_create_device the first time and
+ * gls_ilu_refactor_device afterwards, so nothing of the coarse matrix visits
+ * the host after the first setup.  Called after gls_mg_set_coarse_ilu and
+ * before the first setup (an error otherwise).  Default off: the device
+ * matrix sums its entries in another order than the host one, so the factors
+ * differ in the last bits. */
+glsStatus gls_mg_set_coarse_ilu_device(glsMG mg, int on);
 /* the ILU form of the coarse AMG (coarse_amg = 1 needed): every setup builds
  * the hierarchy with these smoother / coarsest-solve parameters */
 glsStatus gls_mg_set_coarse_amg_ilu(glsMG mg, const glsAMGIluParams *prm);

@@ -488,6 +488,21 @@ public:
     check(gls_ilu_refactor(h, A.vals.data()), "gls_ilu_refactor");
   }
 
+  // the same from the device matrix (Operator::system_matrix_device): the
+  // symbolic phase on the host from a copy of the pattern, the numeric phase
+  // on the device, bitwise equal to the host's on the same values
+  ILU(const glsDeviceCSR &A, const glsILUParams &prm, void *stream = nullptr)
+  {
+    check(gls_ilu_create_device(&A, &prm, stream, &h), "gls_ilu_create_device");
+  }
+
+  // new values on the same pattern, factorised on the device on `stream`
+  void
+  refactor_device(const glsDeviceCSR &A, void *stream = nullptr)
+  {
+    check(gls_ilu_refactor_device(h, A.vals, stream), "gls_ilu_refactor_device");
+  }
+
   // dst = U^-1 L^-1 src (device FP64 vectors, dst != src)
   void
   vmult(double *dst, const double *src, void *stream = nullptr) const
