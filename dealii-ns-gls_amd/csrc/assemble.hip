@@ -355,6 +355,8 @@ op_system_matrix_device(glsOp_ *op, hipStream_t s)
           else
             launch_gather<float>(op, M, E, b, e, s);
         }
+      // node constraints: C^T A C on the same pattern
+      nc_csr_device(op, M->d_row_ptr, M->d_cols, M->d_vals, s);
     }
   catch (...)
     {

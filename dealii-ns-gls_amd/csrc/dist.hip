@@ -600,6 +600,9 @@ gls_dist_create(glsOp op, const glsDistDesc *desc, glsDist *out)
     throw std::runtime_error("gls_dist_create: null argument");
   if (op->faces.n)
     throw std::runtime_error("gls_dist_create: outflow faces are single-domain only");
+  if (op->nc.n)
+    throw std::runtime_error("gls_dist_create: node constraints are single-domain only "
+                             "(partitioned operators with node constraints are not supported)");
   if (desc->world < 1 || desc->rank < 0 || desc->rank >= desc->world)
     throw std::runtime_error("gls_dist_create: bad rank / world");
   HIP_THROW(hipSetDevice(op->device));

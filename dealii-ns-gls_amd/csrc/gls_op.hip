@@ -1245,6 +1245,25 @@ init_dst(const glsOp_ *op, void *dst, const void *src, hipStream_t s)
     launch_init<float>(op, dst, src, s);
 }
 
+// the cell loop and the outflow faces: A x with the Dirichlet identity rows,
+// without the node constraints
+void
+vmult_unwrapped(const glsOp_ *op, void *dst, const void *src, hipStream_t s)
+{
+  ApplyFn   af;
+  ProduceFn pf;
+  select(op, af, pf);
+  if (op->use_brick)
+    select_brick(op)(op, vmult_mode(op), dst, src, 0, op->n_bricks, BRICK_RUN | BRICK_REDUCE, s,
+                     nullptr);
+  else
+    {
+      init_dst(op, dst, src, s);
+      af(op, vmult_mode(op), false, dst, src, 0, op->n_cells, s);
+    }
+  gls::faces_apply(op, false, dst, src, s);
+}
+
 } // namespace
 
 namespace gls
@@ -1259,18 +1278,11 @@ op_vmult_device(glsOp op, void *dst, const void *src, hipStream_t s)
       op_csr_vmult_device(op, dst, src, s);
       return;
     }
-  ApplyFn   af;
-  ProduceFn pf;
-  select(op, af, pf);
-  if (op->use_brick)
-    select_brick(op)(op, vmult_mode(op), dst, src, 0, op->n_bricks, BRICK_RUN | BRICK_REDUCE, s,
-                     nullptr);
-  else
-    {
-      init_dst(op, dst, src, s);
-      af(op, vmult_mode(op), false, dst, src, 0, op->n_cells, s);
-    }
-  faces_apply(op, false, dst, src, s);
+  // node constraints: C^T A C around the unchanged cell loop; the source's
+  // eliminated components are replaced in place and restored
+  nc_resolve(op, const_cast<void *>(src), true, s);
+  vmult_unwrapped(op, dst, src, s);
+  nc_transpose(op, dst, const_cast<void *>(src), false, s);
 }
 
 // the pieces of vmult dist.hip orchestrates around the ghost exchange
@@ -2006,6 +2018,7 @@ gls_op_destroy(glsOp op)
   gls::system_matrix_release(op);
   gls::faces_release(op);
   gls::forces_release(op);
+  gls::nc_release(op);
   delete op;
 }
 
@@ -2168,6 +2181,9 @@ gls_op_vmult_cells(glsOp op, void *dst, const void *src, int64_t b, int64_t e, v
     throw std::runtime_error("gls_op_vmult_cells: bad cell range");
   if (op->faces.n)
     throw std::runtime_error("gls_op_vmult_cells: operators with outflow faces run gls_op_vmult");
+  if (op->nc.n)
+    throw std::runtime_error("gls_op_vmult_cells: operators with node constraints are not "
+                             "supported, they run gls_op_vmult");
   ApplyFn   af;
   ProduceFn pf;
   select(op, af, pf);
@@ -2292,13 +2308,30 @@ gls_op_set_constraint_values(glsOp op, const void *values, void *stream)
     }
   else
     {
-      if (!op->d_inhom)
-        HIP_THROW(hipMalloc(&op->d_inhom, std::max<size_t>(1, (size_t)op->n_dofs * op->tsize())));
+      const size_t bytes = (size_t)op->n_dofs * op->tsize();
       // host or device pointer (hipMemcpyDefault); a caller numbering is
       // permuted through the staging buffers first
       const void *v = op->stage.d_map ? op->stage.in_vec(values, 1, s) : values;
-      HIP_THROW(hipMemcpyAsync(op->d_inhom, v, (size_t)op->n_dofs * op->tsize(),
-                               hipMemcpyDefault, s));
+      if (op->nc.n)
+        {
+          // checked in a copy first: refused values leave the ones set before
+          void *chk = nullptr;
+          HIP_THROW(hipMalloc(&chk, std::max<size_t>(1, bytes)));
+          try
+            {
+              HIP_THROW(hipMemcpyAsync(chk, v, bytes, hipMemcpyDefault, s));
+              gls::nc_check_values(op, chk, s);
+            }
+          catch (...)
+            {
+              (void)hipFree(chk);
+              throw;
+            }
+          (void)hipFree(chk);
+        }
+      if (!op->d_inhom)
+        HIP_THROW(hipMalloc(&op->d_inhom, std::max<size_t>(1, bytes)));
+      HIP_THROW(hipMemcpyAsync(op->d_inhom, v, bytes, hipMemcpyDefault, s));
       op->stage.done(s);
     }
   GLS_CATCH
@@ -2337,7 +2370,9 @@ gls_op_evaluate_rhs(glsOp op, void *dst, void *stream)
   hipStream_t s = (hipStream_t)stream;
   void       *y = op->stage.out_vec(dst);
   distribute(op, op->d_tmp, nullptr, s);
+  gls::nc_resolve(op, op->d_tmp, false, s);
   residual_cells(op, y, op->d_tmp, s);
+  gls::nc_transpose(op, y, nullptr, true, s);
   op->stage.finish_out(dst, s);
   op->stage.done(s);
   GLS_CATCH
@@ -2357,7 +2392,9 @@ gls_op_evaluate_residual(glsOp op, void *dst, const void *src, void *stream)
   void       *y = op->stage.out_vec(dst);
   // operator_ns.cc:655-656: tmp = src; constraints_inhomogeneous.distribute(tmp)
   distribute(op, op->d_tmp, x, s);
+  gls::nc_resolve(op, op->d_tmp, false, s);
   residual_cells(op, y, op->d_tmp, s);
+  gls::nc_transpose(op, y, nullptr, true, s);
   op->stage.finish_out(dst, s);
   op->stage.done(s);
   GLS_CATCH
@@ -2375,7 +2412,9 @@ gls_op_evaluate_residual_plain(glsOp op, void *dst, const void *src, void *strea
   hipStream_t s = (hipStream_t)stream;
   const void *x = op->stage.in_vec(src, 0, s);
   void       *y = op->stage.out_vec(dst);
+  // src is read as it is (already distributed); the rows are transposed
   residual_cells(op, y, x, s);
+  gls::nc_transpose(op, y, nullptr, true, s);
   op->stage.finish_out(dst, s);
   op->stage.done(s);
   GLS_CATCH
@@ -2408,6 +2447,7 @@ gls_op_compute_diagonal(glsOp op, void *diag, void *stream)
   (op->prec == GLS_F64 ? select_diag_t<double>(op->dim, op->degree) :
                          select_diag_t<float>(op->dim, op->degree))(op, vmult_mode(op), d64, s);
   gls::faces_diagonal(op, d64, true, s);
+  gls::nc_diagonal(op, d64, vmult_unwrapped, s);
   if (op->prec == GLS_F64)
     hipLaunchKernelGGL(k_diag_out<double>, grid1d(op->n_dofs), dim3(256), 0, s, (double *)diag,
                        (const double *)d64, op->d_cbits, op->n_owned_dofs, op->n_dofs);
@@ -2510,6 +2550,7 @@ op_inverse_diagonal_device(glsOp op, void *diag, hipStream_t s)
       (op->prec == GLS_F64 ? select_diag_t<double>(op->dim, op->degree) :
                              select_diag_t<float>(op->dim, op->degree))(op, vmult_mode(op), d64, s);
       faces_diagonal(op, d64, true, s);
+      nc_diagonal(op, d64, vmult_unwrapped, s);
       if (op->prec == GLS_F64)
         hipLaunchKernelGGL(k_invert_diag64<double>, grid1d(op->n_dofs), dim3(256), 0, s,
                            (double *)diag, (const double *)d64, op->d_cbits, op->n_owned_dofs,
@@ -2806,6 +2847,9 @@ gls_op_system_matrix(glsOp op, int64_t *nnz, int64_t *row_ptr, int64_t *cols, do
             }
         }
     }
+  // node constraints: C^T A C on the same pattern
+  if (op->nc.n)
+    gls::nc_csr_host(op, row_ptr, cols, vals);
   GLS_CATCH
 }
 

@@ -620,6 +620,11 @@ struct glsMG_
   int                prec = GLS_F32, dim = 3, degree = 2, nc = 4;
   std::vector<uint32_t *> d_child;  // level l >= 1: [cells(l-1)][nl]
   std::vector<void *>     d_weight; // level l >= 1: [n_dofs(l)]
+  // the weights without node constraints (host) and the fine operator's
+  // nc_version they were last uploaded for: gls_mg_setup zeroes the weights of
+  // the eliminated fine components when a level's rows changed
+  std::vector<std::vector<double>> h_weight;
+  std::vector<uint64_t>            weight_nc_version;
   std::vector<void *>     invdiag, sol, def, tmp;
   // deferred shared-node reductions of the smoother (smooth): per level two
   // partial-slot buffers the applies alternate between (beside the
@@ -828,10 +833,21 @@ transfer(const glsMG_ *mg, int kind, int level, void *dst, const void *src, hipS
 {
   if (level < 1 || level >= (int)mg->ops.size())
     throw std::runtime_error("multigrid transfer: level out of range");
+  // node constraints of the coarse level (C_c): the prolongation reads
+  // C_c x_c (the source resolved in place and restored), the restriction ends
+  // with C_c^T and zero on the eliminated coarse components (dst's eliminated
+  // components are zero before: a defect of the constrained operator)
+  const glsOp_ *cop = mg->ops[level - 1];
+  if (kind == 0)
+    gls::nc_resolve(cop, const_cast<void *>(src), true, s);
   if (mg->prec == GLS_F64)
     transfer_p<double>(mg, kind, level, dst, src, s, base);
   else
     transfer_p<float>(mg, kind, level, dst, src, s, base);
+  if (kind == 0)
+    gls::nc_restore(cop, const_cast<void *>(src), s);
+  else if (kind == 1)
+    gls::nc_transpose(cop, dst, nullptr, true, s);
 }
 
 void
@@ -2592,8 +2608,11 @@ power_iteration_t(glsMG_ *mg, int l, hipStream_t s)
   // start vector on the device: mean of i % 11 over [0, n) in closed form
   const int64_t q11  = n / 11, r11 = n % 11;
   const double  mean = n > 0 ? (double)(q11 * 55 + r11 * (r11 - 1) / 2) / (double)n : 0.0;
-  hipLaunchKernelGGL(k_power_start<T>, g1(n), dim3(256), 0, s, (T *)x, op->d_node_cmask,
-                     op->dim + 1, mean, part, n);
+  // "constrained" for the start vector: the Dirichlet mask and the
+  // components the node constraints eliminate
+  hipLaunchKernelGGL(k_power_start<T>, g1(n), dim3(256), 0, s, (T *)x,
+                     op->nc.n ? op->nc.d_cmask_all : op->d_node_cmask, op->dim + 1, mean, part,
+                     n);
   hipLaunchKernelGGL(k_power_finish, dim3(1), dim3(256), 0, s, (const double *)part, nb, scal);
   hipLaunchKernelGGL(k_scale_dev<T>, g1(n), dim3(256), 0, s, (T *)x, (const T *)x,
                      (const double *)scal, n);
@@ -2681,6 +2700,8 @@ gls_mg_create(const glsMGDesc *desc, const glsOp *levels, const uint32_t *const 
     }
   mg->d_child.assign(nl_levels, nullptr);
   mg->d_weight.assign(nl_levels, nullptr);
+  mg->h_weight.assign(nl_levels, std::vector<double>());
+  mg->weight_nc_version.assign(nl_levels, 0);
   for (int l = 1; l < nl_levels; ++l)
     {
       glsOp         cop = mg->ops[l - 1], fop = mg->ops[l];
@@ -2721,6 +2742,7 @@ gls_mg_create(const glsMGDesc *desc, const glsOp *levels, const uint32_t *const 
       HIP_THROW(hipMalloc((void **)&mg->d_child[l], nch * sizeof(uint32_t)));
       HIP_THROW(hipMemcpy(mg->d_child[l], ch.data(), nch * sizeof(uint32_t),
                           hipMemcpyHostToDevice));
+      mg->h_weight[l] = w;
       HIP_THROW(hipMalloc(&mg->d_weight[l], w.size() * mg->ts()));
       if (mg->prec == GLS_F64)
         HIP_THROW(hipMemcpy(mg->d_weight[l], w.data(), w.size() * 8, hipMemcpyHostToDevice));
@@ -2824,6 +2846,36 @@ gls_mg_setup(glsMG mg, void *stream)
       throw std::runtime_error("gls_mg_setup: level " + std::to_string(l) +
                                " is in matrix-based mode (gls_op_set_matrix_based); level "
                                "operators stay matrix-free");
+  // the direct coarse solvers assemble from element matrices themselves and
+  // know the Dirichlet mask only
+  if (mg->desc.coarse_n_iterations < 0 && !mg->desc.coarse_amg && mg->ops[0]->nc.n)
+    throw std::runtime_error(
+      mg->coarse_method == GLS_COARSE_ND ?
+        "gls_mg_setup: the nested-dissection (\"nd\") direct coarse solver does not support a "
+        "coarse operator with node constraints" :
+        "gls_mg_setup: the dense Schur-complement direct coarse solver does not support a "
+        "coarse operator with node constraints");
+  // node constraints: the transfer weights are zero on the eliminated fine
+  // components, as on the Dirichlet ones; rebuilt when a level's rows changed
+  for (size_t l = 1; l < mg->ops.size(); ++l)
+    {
+      const glsOp fop = mg->ops[l];
+      if (mg->weight_nc_version[l] == fop->nc_version)
+        continue;
+      gls::DeviceScope dev(fop->device);
+      HIP_THROW(hipStreamSynchronize((hipStream_t)stream));
+      std::vector<double> w = mg->h_weight[l];
+      for (int64_t i = 0; i < fop->nc.n; ++i)
+        w[(size_t)(fop->nc.h_node[(size_t)i] * mg->nc + fop->nc.h_comp[(size_t)i])] = 0.0;
+      if (mg->prec == GLS_F64)
+        HIP_THROW(hipMemcpy(mg->d_weight[l], w.data(), w.size() * 8, hipMemcpyHostToDevice));
+      else
+        {
+          std::vector<float> wf(w.begin(), w.end());
+          HIP_THROW(hipMemcpy(mg->d_weight[l], wf.data(), wf.size() * 4, hipMemcpyHostToDevice));
+        }
+      mg->weight_nc_version[l] = fop->nc_version;
+    }
   // every allocation and launch of the setup (the AMG hierarchy included)
   // on the levels' device; the caller's current device is restored
   gls::DeviceScope dev(mg->ops[0]->device);

@@ -61,6 +61,41 @@ struct OutflowFaces
   void               *d_target = nullptr; // [n][nqf][dim] face_target_velocity
 };
 
+// node constraints (node_constraints.hip): rows (node, comp, coef[dim]),
+// u[node][comp] = sum_e coef[e] u[node][e], at most one per node, nodes
+// ascending; C is block diagonal over the nodes and vmult computes C^T A C
+// (identity on the eliminated rows) around the unchanged cell loop
+struct NodeConstraints
+{
+  int64_t              n = 0;
+  std::vector<int64_t> h_node;
+  std::vector<int32_t> h_comp;
+  std::vector<double>  h_coef; // [n][dim]
+  int64_t *d_node = nullptr;
+  int32_t *d_comp = nullptr;
+  void    *d_coef = nullptr;   // [n][dim], the operator's precision
+  void    *d_save = nullptr;   // [n] the source's eliminated values during a vmult
+  // diagonal of C^T A C: rows grouped by colour (no two nodes of a colour
+  // share a cell), row list d_rows, colour k at [colour_off[k], colour_off[k+1]);
+  // a unit-vector sum and its image (d_unit, d_image: [n_dofs]); per row the
+  // column and the row `comp` of the node's velocity block (d_block: [n][2][dim])
+  std::vector<int64_t> colour_off;
+  // system matrix (k_nc_csr_*): node -> row (-1: none), the nodes that share
+  // a cell with a listed node (their matrix rows hold the listed columns),
+  // the coefficients in FP64
+  std::vector<int32_t> h_row_of, h_adj;
+  int32_t *d_row_of = nullptr;
+  int32_t *d_adj    = nullptr;
+  // [n_nodes] the Dirichlet mask with the eliminated components added: what
+  // "constrained dof" means to the multigrid's power-iteration start vector
+  uint8_t *d_cmask_all = nullptr;
+  double  *d_coef64 = nullptr;
+  int32_t *d_rows  = nullptr;
+  void    *d_unit  = nullptr;
+  void    *d_image = nullptr;
+  double  *d_block = nullptr;
+};
+
 // drag / lift faces and the solution probe (forces.hip): per face the
 // internal cell, the face number and the cell's node coordinates; per probe
 // pair the internal cell and the reference point, grouped by point
@@ -138,6 +173,10 @@ struct glsOp_
   gls::VecStage stage; // caller vector layout (host memory / dof permutation)
   gls::OutflowFaces faces; // weak outflow boundary faces (faces.hip)
   gls::Forces forces;      // drag / lift faces and probe points (forces.hip)
+  gls::NodeConstraints nc; // no-normal-flux rows (node_constraints.hip)
+  // bumped by gls_op_set_node_constraints: gls_mg_setup rebuilds the transfer
+  // weights of a level whose rows changed
+  uint64_t nc_version = 0;
   // the system matrix on the device (assemble.hip): made at the first use,
   // its values valid until an entry point changes what vmult computes
   // (op_invalidate_system) or gls_op_invalidate_system; matrix_based: vmult
@@ -285,7 +324,7 @@ inline bool
 deferred_reduce_ok(const glsOp_ *op)
 {
   return op->use_brick && op->n_owned_dofs == op->n_dofs && op->faces.n == 0 &&
-         op->prec == GLS_F32 && op->dim == 3 && op->reduce_classes.n > 0;
+         op->nc.n == 0 && op->prec == GLS_F32 && op->dim == 3 && op->reduce_classes.n > 0;
 }
 
 // the pieces of vmult that dist.hip / mg.hip orchestrate (gls_op.hip):
@@ -323,6 +362,32 @@ void faces_linearization(const glsOp_ *op, const void *lin, hipStream_t s);
 void faces_apply(const glsOp_ *op, bool residual, void *dst, const void *src, hipStream_t s);
 void faces_diagonal(const glsOp_ *op, void *diag, bool f64_out, hipStream_t s);
 void faces_element_matrices(const glsOp_ *op, void *emat, int64_t b, int64_t e, hipStream_t s);
+// node constraints (node_constraints.hip).  resolve: v[node][comp] <- sum_e
+// coef[e] v[node][e], the old value kept in d_save (save) or dropped.
+// transpose: r = dst[node][comp]; dst[node][e] += coef[e] r; dst[node][comp]
+// <- the saved value (identity row) or 0 (zero); restore_src: src[node][comp]
+// <- the saved value.  One lane per row; no allocation, no synchronisation.
+void nc_release(glsOp_ *op);
+// throws when a node with a row has a non-zero constraint value on a
+// Dirichlet component of the device vector d_values (null: nothing to check;
+// copies it to the host: synchronises)
+void nc_check_values(const glsOp_ *op, const void *d_values, hipStream_t s);
+void nc_resolve(const glsOp_ *op, void *v, bool save, hipStream_t s);
+void nc_transpose(const glsOp_ *op, void *dst, void *restore_src, bool zero, hipStream_t s);
+// v[node][comp] <- the value nc_resolve(save) kept
+void nc_restore(const glsOp_ *op, void *v, hipStream_t s);
+// the rows' entries of the FP64 diagonal d64 of C^T A C from the assembled
+// diagonal of A in d64; apply: the unwrapped operator (cell loop and faces)
+void nc_diagonal(const glsOp_ *op, double *d64,
+                 void (*apply)(const glsOp_ *, void *, const void *, hipStream_t), hipStream_t s);
+// the CSR of A (rows of constrained dofs: unit diagonal only; the rows of one
+// node share one column pattern) made the CSR of C^T A C in place: every
+// node-pair block P_I^T B P_J, unit diagonal and zero off-diagonals on the
+// eliminated rows and columns; the pattern stays.  Device (cols int32) and
+// host (cols int64) versions of one algorithm.
+void nc_csr_device(const glsOp_ *op, const int64_t *row_ptr, const int32_t *cols, double *vals,
+                   hipStream_t s);
+void nc_csr_host(const glsOp_ *op, const int64_t *row_ptr, const int64_t *cols, double *vals);
 // surface force and probe lists (forces.hip)
 void forces_release(glsOp_ *op);
 // the probe values of the local cells into host values[n_points][dim + 1],
@@ -331,11 +396,12 @@ void forces_release(glsOp_ *op);
 void probe_run(glsOp_ *op, const void *vec, bool avg, double *values, hipStream_t s);
 const std::vector<int64_t> &probe_counts(const glsOp_ *op);
 // the brick vmult with the smoother step fused into its write-out needs the
-// whole A x inside the kernel: single domain, no face terms
+// whole A x inside the kernel: single domain, no face terms, no node
+// constraints
 inline bool
 fused_relax_ok(const glsOp_ *op)
 {
-  return op->use_brick && op->n_owned_dofs == op->n_dofs && op->faces.n == 0;
+  return op->use_brick && op->n_owned_dofs == op->n_dofs && op->faces.n == 0 && op->nc.n == 0;
 }
 
 // team primitives of the partitioned multigrid / GMRES (dist.hip): the ranks

@@ -32,6 +32,7 @@
 
 #include <algorithm>
 #include <array>
+#include <cfloat>
 #include <cmath>
 #include <cstring>
 #include <map>
@@ -1016,6 +1017,247 @@ gls_mesh_constraint_mask(const glsMesh *m, uint32_t vel_ids, uint32_t p_ids,
       out[i] = mask;
     }
   return 0;
+}
+
+int
+gls_mesh_no_normal_flux(const glsMesh *m, uint32_t slip_ids, uint32_t dirichlet_vel_ids,
+                        int64_t *n, int64_t *nodes, int32_t *comp, double *coef,
+                        double *normals)
+{
+  if (!m || !n)
+    {
+      g_err = "gls_mesh_no_normal_flux: null argument";
+      return 1;
+    }
+  if (nodes && (!comp || !coef))
+    {
+      g_err = "gls_mesh_no_normal_flux: nodes without comp / coef";
+      return 1;
+    }
+  const int dim = m->dim, k = m->degree, kp = k + 1;
+  const int nloc = dim == 3 ? kp * kp * kp : kp * kp;
+  // only curved or oblique ids give rows; the planar ones are components of
+  // the Dirichlet mask (gls_mesh_constraint_mask)
+  slip_ids &= m->nonplanar_bids;
+  // 1D Lagrange derivatives at the support points (equidistant for k <= 2):
+  // dl[j][i] = l_i'(x_j)
+  double dl[3][3] = {};
+  if (k == 1)
+    for (int j = 0; j < 2; ++j)
+      {
+        dl[j][0] = -1.0;
+        dl[j][1] = 1.0;
+      }
+  else if (k == 2)
+    {
+      const double t[3][3] = {{-3, 4, -1}, {-1, 0, 1}, {1, -4, 3}};
+      for (int j = 0; j < 3; ++j)
+        for (int i = 0; i < 3; ++i)
+          dl[j][i] = t[j][i];
+    }
+  else
+    {
+      g_err = "gls_mesh_no_normal_flux: degree must be 1 or 2";
+      return 1;
+    }
+  struct Acc
+  {
+    double sum[3]  = {0, 0, 0}; // over the cells: their normalised face averages
+    double cell[3] = {0, 0, 0}; // over the faces of the current cell
+    int64_t last   = -1;        // current cell
+  };
+  struct FaceNormal
+  {
+    uint32_t node;
+    double   v[3];
+  };
+  struct Row
+  {
+    uint32_t node;
+    double   s[3]; // the averaged unit normal
+  };
+  std::vector<Row> rows;
+  // one boundary id at a time, as the reference calls
+  // compute_no_normal_flux_constraints once per id (main.cc:285-287): only
+  // the faces of that id enter a node's normal
+  for (int bid = 0; bid < 32; ++bid)
+    {
+  if (!((slip_ids >> bid) & 1))
+    continue;
+  const uint32_t                    one = 1u << bid;
+  std::unordered_map<uint32_t, Acc> acc;
+  std::vector<FaceNormal>           face_normals;
+  auto close_cell = [&](Acc &a) {
+    const double len = std::sqrt(a.cell[0] * a.cell[0] + a.cell[1] * a.cell[1] +
+                                 a.cell[2] * a.cell[2]);
+    if (len > 0)
+      for (int d = 0; d < 3; ++d)
+        a.sum[d] += a.cell[d] / len;
+    a.cell[0] = a.cell[1] = a.cell[2] = 0;
+  };
+  for (int64_t c = 0; c < m->n_cells; ++c)
+    {
+      const uint32_t *cn = &m->cell_nodes[(size_t)c * nloc];
+      for (int f = 0; f < 2 * dim; ++f)
+        {
+          const int a = f / 2, side = f % 2;
+          uint32_t  common = one;
+          for (int p = 0; p < nloc; ++p)
+            {
+              const int idx[3] = {p % kp, (p / kp) % kp, p / (kp * kp)};
+              if (idx[a] == side * k)
+                common &= m->node_bid[cn[p]];
+            }
+          if (!common)
+            continue;
+          for (int p = 0; p < nloc; ++p)
+            {
+              const int idx[3] = {p % kp, (p / kp) % kp, p / (kp * kp)};
+              if (idx[a] != side * k)
+                continue;
+              // Jacobian of the cell's Q_k map at this support point
+              double J[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
+              for (int d = 0; d < dim; ++d)
+                for (int b = 0; b < dim; ++b)
+                  {
+                    double s = 0;
+                    for (int i = 0; i < kp; ++i)
+                      {
+                        int q[3] = {idx[0], idx[1], idx[2]};
+                        q[b]     = i;
+                        s += dl[idx[b]][i] *
+                             m->coords[(size_t)cn[q[0] + kp * (q[1] + kp * q[2])] * dim + d];
+                      }
+                    J[d][b] = s;
+                  }
+              // J^-T e_a up to the positive factor det J: the cofactors of column a
+              double nv[3] = {0, 0, 0};
+              if (dim == 2)
+                {
+                  const int b = 1 - a;
+                  const double sg = a == 0 ? 1.0 : -1.0;
+                  nv[0] = sg * J[1][b];
+                  nv[1] = -sg * J[0][b];
+                }
+              else
+                {
+                  const int b = (a + 1) % 3, e = (a + 2) % 3;
+                  nv[0] = J[1][b] * J[2][e] - J[2][b] * J[1][e];
+                  nv[1] = J[2][b] * J[0][e] - J[0][b] * J[2][e];
+                  nv[2] = J[0][b] * J[1][e] - J[1][b] * J[0][e];
+                }
+              if (!side)
+                for (int d = 0; d < 3; ++d)
+                  nv[d] = -nv[d];
+              double len = std::sqrt(nv[0] * nv[0] + nv[1] * nv[1] + nv[2] * nv[2]);
+              if (!(len > 0))
+                {
+                  g_err = "gls_mesh_no_normal_flux: degenerate face at node " +
+                          std::to_string(cn[p]);
+                  return 2;
+                }
+              for (int d = 0; d < 3; ++d)
+                {
+                  nv[d] /= len;
+                  if (std::abs(nv[d]) < 1e-13)
+                    nv[d] = 0;
+                }
+              len = std::sqrt(nv[0] * nv[0] + nv[1] * nv[1] + nv[2] * nv[2]);
+              Acc &ac = acc[cn[p]];
+              if (ac.last != c)
+                {
+                  close_cell(ac);
+                  ac.last = c;
+                }
+              FaceNormal fn;
+              fn.node = cn[p];
+              for (int d = 0; d < 3; ++d)
+                {
+                  nv[d] /= len;
+                  ac.cell[d] += nv[d];
+                  fn.v[d] = nv[d];
+                }
+              face_normals.push_back(fn);
+            }
+        }
+    }
+  for (auto &kv : acc)
+    {
+      close_cell(kv.second);
+      double *s = kv.second.sum;
+      const double len = std::sqrt(s[0] * s[0] + s[1] * s[1] + s[2] * s[2]);
+      if (!(len > 0))
+        {
+          g_err = "gls_mesh_no_normal_flux: the face normals at node " +
+                  std::to_string(kv.first) + " cancel (a corner inside one boundary id)";
+          return 3;
+        }
+      for (int d = 0; d < 3; ++d)
+        s[d] /= len;
+      rows.push_back(Row{kv.first, {s[0], s[1], s[2]}});
+    }
+  // a corner inside one id: some face normal is more than 60 degrees off the
+  // average.  This path models smooth surfaces only.
+  for (const FaceNormal &fn : face_normals)
+    {
+      const double *s = acc[fn.node].sum;
+      if (fn.v[0] * s[0] + fn.v[1] * s[1] + fn.v[2] * s[2] < 0.5)
+        {
+          g_err = "gls_mesh_no_normal_flux: node " + std::to_string(fn.node) +
+                  " is a corner of the slip boundary (face normals more than 60 degrees "
+                  "from their average); corners are not modelled";
+          return 3;
+        }
+    }
+    } // boundary ids
+  std::sort(rows.begin(), rows.end(), [](const Row &a, const Row &b) { return a.node < b.node; });
+  for (size_t i = 1; i < rows.size(); ++i)
+    if (rows[i].node == rows[i - 1].node)
+      {
+        g_err = "gls_mesh_no_normal_flux: node " + std::to_string(rows[i].node) +
+                " lies on two curved slip boundary ids; more than one row per node is not "
+                "supported";
+        return 4;
+      }
+  int64_t count = 0;
+  for (const Row &row : rows)
+    {
+      const uint32_t node = row.node;
+      // every velocity component of a node on a Dirichlet id is fixed: the
+      // eliminated one too, so there is no row
+      if (m->node_bid[node] & dirichlet_vel_ids)
+        continue;
+      if (nodes)
+        {
+          const double *s  = row.s;
+          double        mx = 0;
+          for (int d = 0; d < dim; ++d)
+            mx = std::max(mx, std::abs(s[d]));
+          int cd = 0;
+          while (std::abs(s[cd]) < (1.0 - 1e-10) * mx)
+            ++cd;
+          nodes[count] = node;
+          comp[count]  = cd;
+          for (int d = 0; d < dim; ++d)
+            {
+              double v = d == cd ? 0.0 : -s[d] / s[cd];
+              if (std::abs(v) <= DBL_EPSILON)
+                v = 0.0;
+              coef[(size_t)count * dim + d] = v;
+              if (normals)
+                normals[(size_t)count * dim + d] = s[d];
+            }
+        }
+      ++count;
+    }
+  *n = count;
+  return 0;
+}
+
+uint32_t
+gls_mesh_nonplanar_ids(const glsMesh *m)
+{
+  return m ? m->nonplanar_bids : 0u;
 }
 
 int

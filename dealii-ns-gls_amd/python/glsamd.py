@@ -60,6 +60,7 @@ EXPORTS = [
     "gls_assemble_plan_host",
     "gls_ilu_refactor_device", "gls_ilu_create_device", "gls_ilu_factor_info",
     "gls_ilu_factor_host", "gls_mg_set_coarse_ilu_device",
+    "gls_op_set_node_constraints", "gls_op_n_node_constraints", "gls_op_distribute",
 ]
 
 GLS_PREC_MG, GLS_PREC_ILU, GLS_PREC_AMG = 0, 1, 2
@@ -258,6 +259,9 @@ def lib():
         L.gls_op_evaluate_residual_plain.argtypes = [vp, vp, vp, vp]
         L.gls_op_evaluate_rhs.argtypes = [vp, vp, vp]
         L.gls_op_set_constraint_values.argtypes = [vp, vp, vp]
+        L.gls_op_set_node_constraints.argtypes = [vp, i64, vp, vp, vp, vp]
+        L.gls_op_n_node_constraints.argtypes = [vp, C.POINTER(i64), C.POINTER(C.c_int)]
+        L.gls_op_distribute.argtypes = [vp, vp, C.c_int, vp]
         L.gls_op_compute_inverse_diagonal.argtypes = [vp, vp, vp]
         L.gls_op_upload_tables.argtypes = [vp, vp, vp]
         L.gls_op_download_tables.argtypes = [vp, vp, vp]
@@ -531,7 +535,7 @@ class NavierStokesOperator:
     (MG levels, MGNumber=float, config.h:6-7)."""
 
     def __init__(self, mesh, cmask, precision="f64", cells=None, n_owned_nodes=None,
-                 brick=None, outflow=None):
+                 brick=None, outflow=None, node_constraints=None):
         import torch
         if not torch.cuda.is_available():
             raise GlsError("NavierStokesOperator needs a GPU (no CPU fallback by design)")
@@ -587,6 +591,36 @@ class NavierStokesOperator:
         dims = (C.c_int * 3)()
         _check(lib().gls_op_brick_shape(h, dims))
         self.brick_shape = tuple(dims)  # what runs: (0, 0, 0) = per-cell kernel
+        if node_constraints is not None:
+            self.set_node_constraints(*node_constraints)
+
+    def set_node_constraints(self, nodes, comp, coef):
+        """No-normal-flux rows u[nodes[i]][comp[i]] = sum_e coef[i][e]
+        u[nodes[i]][e] (Mesh.node_constraints / Deck.node_constraints;
+        gls_op_set_node_constraints): vmult becomes C^T A C with identity rows
+        on the eliminated components.  Empty arrays clear."""
+        nodes = np.ascontiguousarray(nodes, dtype=np.int64).ravel()
+        comp = np.ascontiguousarray(comp, dtype=np.int32).ravel()
+        coef = np.ascontiguousarray(coef, dtype=np.float64).reshape(-1)
+        if len(comp) != len(nodes) or len(coef) != len(nodes) * self.dim:
+            raise GlsError("set_node_constraints: expected nodes [n], comp [n], coef [n][dim]")
+        _check(lib().gls_op_set_node_constraints(self.h, len(nodes), nodes.ctypes.data,
+                                                 comp.ctypes.data, coef.ctypes.data, _stream()))
+        self.node_constraint_rows = (nodes, comp, coef.reshape(-1, self.dim))
+
+    @property
+    def n_node_constraints(self):
+        """(rows, colours of the diagonal's unit-vector applies)."""
+        n, c = C.c_int64(), C.c_int()
+        _check(lib().gls_op_n_node_constraints(self.h, C.byref(n), C.byref(c)))
+        return n.value, c.value
+
+    def distribute(self, vec, homogeneous=False):
+        """AffineConstraints::distribute in place (gls_op_distribute):
+        Dirichlet components take 0 (homogeneous) or the constraint values,
+        eliminated components their rows' combination."""
+        _check(lib().gls_op_distribute(self.h, _vptr(vec), 1 if homogeneous else 0, _stream()))
+        return vec
 
     def extract_constant_modes(self):
         """NavierStokesOperator::extract_constant_modes (operator_ns.cc:
@@ -1605,26 +1639,33 @@ class Multigrid:
 
 
 def build_gmg(meshes, cmasks, params, u_star_fine, history_fine=None, weights=None,
-              precision="f32", coarse_iso_q1=False, outflow=None, **mg_kwargs):
+              precision="f32", coarse_iso_q1=False, outflow=None, node_constraints=None,
+              **mg_kwargs):
     """Level operators + transfers for a mesh hierarchy (coarse -> fine), the
     linearization point / history interpolated down level by level
     (interpolate_to_mg, main.cc:772-803, 815-832).  coarse_iso_q1: the
     coarsest level with FE_Q_iso_Q1 (glsmesh.IsoQ1Mesh, main.cc:436-446).
     outflow: None, or (kind, boundary id): every level operator gets its
     mesh's outflow faces (the level operators take the outflow sets too,
-    main.cc:520-527).  Returns (mg, level_ops)."""
+    main.cc:520-527).  node_constraints: None, or per level (nodes, comp,
+    coef) or None (Deck.node_constraints of the level's mesh).  Returns
+    (mg, level_ops)."""
     import torch
     if coarse_iso_q1:
         import glsmesh
         meshes = [glsmesh.IsoQ1Mesh(meshes[0])] + list(meshes[1:])
     ops = []
-    for m, cm in zip(meshes, cmasks):
+    if node_constraints is None:
+        node_constraints = [None] * len(meshes)
+    if coarse_iso_q1 and node_constraints[0] is not None:
+        raise GlsError("build_gmg: node constraints on an FE_Q_iso_Q1 level are not supported")
+    for m, cm, rows in zip(meshes, cmasks, node_constraints):
         of = None
         if outflow is not None:
             import glsmesh
             fc, fn = glsmesh.boundary_faces(m, outflow[1])
             of = (fc, fn, outflow[0])
-        op = NavierStokesOperator(m, cm, precision, outflow=of)
+        op = NavierStokesOperator(m, cm, precision, outflow=of, node_constraints=rows)
         op.set_parameters(**params)
         ops.append(op)
     child = [meshes[l - 1].child_lattice(meshes[l]) for l in range(1, len(meshes))]

@@ -45,6 +45,10 @@ def lib():
             getattr(L, name).argtypes = [vp]
             getattr(L, name).restype = vp
         L.gls_mesh_constraint_mask.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp]
+        L.gls_mesh_no_normal_flux.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_int64),
+                                              vp, vp, vp, vp]
+        L.gls_mesh_nonplanar_ids.argtypes = [vp]
+        L.gls_mesh_nonplanar_ids.restype = C.c_uint32
         L.gls_mesh_child_lattice.argtypes = [vp, vp, vp]
         L.gls_mesh_cell_measure.argtypes = [vp, vp, vp]
         L.gls_mesh_brick.argtypes = [vp, vp]
@@ -86,6 +90,8 @@ class Mesh:
                             np.float64).reshape(self.n_nodes, self.dim)
         self.node_boundary = _view(L.gls_mesh_node_boundary(self._h), self.n_nodes, np.uint32)
         self.cell_coarse = _view(L.gls_mesh_cell_coarse(self._h), self.n_cells, np.int32)
+        # bit b: boundary id b has a curved or oblique face (gls_mesh_nonplanar_ids)
+        self.nonplanar_ids = int(L.gls_mesh_nonplanar_ids(self._h))
 
     @property
     def h(self):
@@ -109,6 +115,26 @@ class Mesh:
         _check(lib().gls_mesh_constraint_mask(self._h, bits(vel_ids), bits(p_ids),
                                               bits(slip_ids), out.ctypes.data))
         return out
+
+    def node_constraints(self, slip_ids, vel_ids=()):
+        """(nodes, comp, coef, normals): the no-normal-flux rows of the curved
+        or oblique boundary ids in slip_ids (gls_mesh_no_normal_flux),
+        u[nodes[i]][comp[i]] = sum_e coef[i][e] u[nodes[i]][e]; nodes on an id
+        of vel_ids (velocity Dirichlet) have none."""
+        bits = lambda ids: sum(1 << int(i) for i in ids)
+        n = C.c_int64(0)
+        L = lib()
+        _check(L.gls_mesh_no_normal_flux(self._h, bits(slip_ids), bits(vel_ids), C.byref(n),
+                                         None, None, None, None))
+        nodes = np.zeros(n.value, dtype=np.int64)
+        comp = np.zeros(n.value, dtype=np.int32)
+        coef = np.zeros((n.value, self.dim))
+        normals = np.zeros((n.value, self.dim))
+        if n.value:
+            _check(L.gls_mesh_no_normal_flux(self._h, bits(slip_ids), bits(vel_ids), C.byref(n),
+                                             nodes.ctypes.data, comp.ctypes.data,
+                                             coef.ctypes.data, normals.ctypes.data))
+        return nodes, comp, coef, normals
 
     def brick(self):
         """(bx, by, bz): cells per brick (gls_mesh_brick)."""
@@ -457,6 +483,37 @@ class Deck:
             vel.append(1)  # inhomogeneous DBC with the inflow function
         return vel, p, slip
 
+    def node_constraints(self, mesh):
+        """(nodes, comp, coef) of the no-normal-flux rows on the curved slip
+        ids (the cylinder with "simulation no slip cylinder": false,
+        simulation.cc:425-428, main.cc:285-287): what the operator takes as
+        node_constraints beside mask(mesh).  Empty without such an id."""
+        if hasattr(mesh, "mapping_points"):
+            raise NotImplementedError("node constraints on an FE_Q_iso_Q1 level")
+        vel, _, _, curved = self.split_descriptor(mesh)
+        nodes, comp, coef, _ = mesh.node_constraints(curved, vel)
+        return nodes, comp, coef
+
+    def split_descriptor(self, mesh):
+        """(vel_ids, p_ids, planar slip ids, curved slip ids): the boundary
+        descriptor with its slip ids split by what the mesh says of them
+        (Mesh.nonplanar_ids: an id with a curved or oblique face); the planar
+        ones are components of the Dirichlet mask, the curved ones node
+        constraints."""
+        vel, p, slip = self.boundary_descriptor()
+        base = mesh
+        while not hasattr(base, "nonplanar_ids") and hasattr(base, "base"):
+            base = base.base
+        nonplanar = getattr(base, "nonplanar_ids", 0)
+        curved = [b for b in slip if (nonplanar >> b) & 1]
+        return vel, p, [b for b in slip if b not in curved], curved
+
+    def mask(self, mesh):
+        """The Dirichlet mask of the descriptor without the curved slip ids
+        (those are node_constraints)."""
+        vel, p, planar, _ = self.split_descriptor(mesh)
+        return mesh.constraint_mask(vel, p, planar)
+
     def constraint_values(self, mesh, t=0.0):
         """The inhomogeneity of constraints_inhomogeneous at time t
         (main.cc:879-891, 926-942) as a dof vector: the inflow function
@@ -468,7 +525,8 @@ class Deck:
         keep the value 0.  Nonzero only on constrained components."""
         if self.simulation not in ("cylinder", "sphere"):
             raise NotImplementedError(f"simulation {self.simulation!r} (SURVEY §8f next-4)")
-        vel, p, slip = self.boundary_descriptor()
+        # curved slip ids are node constraints, no Dirichlet values
+        vel, p, slip, _ = self.split_descriptor(mesh)
         inflow_id = 1 if self.simulation == "sphere" else 0
         full = mesh.constraint_mask(vel, p, slip)
         inhom = {inflow_id} | ({1} if self.simulation == "cylinder" and self.outflow == "strong"

@@ -195,11 +195,18 @@ def wire_newton(solver, op, cmask, linear_solver, preconditioner=None):
     operator; setup_preconditioner = GMG initialize at the solution;
     evaluate_rhs / evaluate_residual = the operator's; solve_with_jacobian =
     set_zero(src) on constrained rows, GMRES, distribute(dst) (homogeneous:
-    constrained increments 0)."""
+    constrained increments 0, the components node constraints eliminate take
+    their rows' combination)."""
     import torch
     nc = op.dim + 1
     cm = np.asarray(cmask, dtype=np.uint8)
     con = ((cm[:, None] >> np.arange(nc)[None, :]) & 1).astype(bool).ravel()
+    n_rows = op.n_node_constraints[0] if hasattr(op, "n_node_constraints") else 0
+    if n_rows:
+        # the eliminated rows are identity rows of the Jacobian too
+        nodes = np.asarray(op.node_constraint_rows[0], dtype=np.int64)
+        comps = np.asarray(op.node_constraint_rows[1], dtype=np.int64)
+        con[nodes * nc + comps] = True
     con_t = torch.from_numpy(con).to("cuda")
 
     def setup_jacobian(src):
@@ -219,7 +226,10 @@ def wire_newton(solver, op, cmask, linear_solver, preconditioner=None):
     def solve_with_jacobian(dst, src):
         src.masked_fill_(con_t, 0.0)
         linear_solver.solve(dst, src)
-        dst.masked_fill_(con_t, 0.0)
+        if n_rows:
+            op.distribute(dst, homogeneous=True)
+        else:
+            dst.masked_fill_(con_t, 0.0)
 
     solver.setup_jacobian = setup_jacobian
     solver.setup_preconditioner = setup_preconditioner

@@ -96,6 +96,31 @@ int gls_mesh_constraint_mask(const glsMesh *m, uint32_t vel_ids,
                              uint32_t p_ids, uint32_t slip_ids,
                              uint8_t *out);
 
+/* No-normal-flux (slip) constraints on the curved or oblique boundary ids in
+ * slip_ids (VectorTools::compute_no_normal_flux_constraints with the mapping,
+ * main.cc:285-287); planar axis-aligned ids give no rows, they are components
+ * of gls_mesh_constraint_mask.  One row per boundary node:
+ *   u[node][comp] = sum_e coef[e] * u[node][e],   coef[comp] = 0,
+ * with the node's unit normal n (normals of the cell faces on the id at the
+ * node, from the cell's own Q_k map, averaged per cell and then over the
+ * cells), comp the lowest e with |n_e| >= (1 - 1e-10) max |n|, and
+ * coef[e] = -n_e / n_comp.  Nodes on an id of dirichlet_vel_ids get no row.
+ * A node at which a face normal is more than 60 degrees off the average (a
+ * corner inside one id) is an error.  Count, then fill: with nodes == NULL
+ * only *n is written; otherwise nodes[*n] (ascending), comp[*n],
+ * coef[*n * dim] and, if not NULL, normals[*n * dim].  Several ids in
+ * slip_ids are treated one at a time (only the faces of one id enter a
+ * node's normal); a node on two curved ids would need two rows and is an
+ * error.  Returns 0 on success. */
+int gls_mesh_no_normal_flux(const glsMesh *m, uint32_t slip_ids,
+                            uint32_t dirichlet_vel_ids, int64_t *n,
+                            int64_t *nodes, int32_t *comp, double *coef,
+                            double *normals);
+
+/* Bit b set <=> some boundary face with id b is curved or oblique: such an id
+ * takes gls_mesh_no_normal_flux, the others gls_mesh_constraint_mask. */
+uint32_t gls_mesh_nonplanar_ids(const glsMesh *m);
+
 /* Cells are ordered brick-major inside every coarse cell: bricks of
  * dims[0] x dims[1] x dims[2] cells (min(2^n_ref, 4) per direction in 3D,
  * min(2^n_ref, 8) in 2D), lexicographic inside a brick, so the cell list is

@@ -270,6 +270,43 @@ glsStatus gls_op_evaluate_rhs(glsOp op, void *dst, void *stream);
  * (all constrained values zero).  Copied; call again when the time-dependent
  * boundary values change (every time step in the reference). */
 glsStatus gls_op_set_constraint_values(glsOp op, const void *values, void *stream);
+
+/* Node constraints: no-normal-flux (slip) on curved boundaries
+ * (VectorTools::compute_no_normal_flux_constraints, main.cc:285-287), which
+ * couple the velocity components of a node and are no entries of the
+ * Dirichlet mask.  n rows (host arrays, copied; what
+ * gls_mesh_no_normal_flux returns):
+ *   u[nodes[i]][comp[i]] = sum_e coef[i][e] * u[nodes[i]][e],  coef[i][comp[i]] = 0,
+ * at most one row per node, nodes ascending.  With C the constraint matrix,
+ * vmult computes C^T A C x with identity rows on the eliminated components
+ * (as on the Dirichlet ones), evaluate_rhs / evaluate_residual distribute
+ * the rows too and return C^T r with zeros there, and compute_diagonal /
+ * compute_inverse_diagonal give the diagonal of C^T A C.  glsOpDesc.node_cmask
+ * does not list the eliminated components.  During gls_op_vmult the source
+ * vector's eliminated components are overwritten and restored in place on
+ * the call's stream: it must not be read on another stream meanwhile.
+ * n = 0 clears.  Errors: nodes not ascending and unique, comp no velocity
+ * component or in the node's Dirichlet mask, a non-zero coefficient on comp or
+ * on a Dirichlet component, a partitioned operator.  gls_op_system_matrix and
+ * gls_op_system_matrix_device give C^T A C on the pattern of A, so
+ * matrix-based mode, ILU and AMG take such an operator as any other; a
+ * multigrid takes levels with rows (the transfers apply the coarse level's C
+ * and C^T, such levels run the unfused smoother; gls_mg_setup re-reads the
+ * rows).  Refused on an operator with rows: gls_op_vmult_cells,
+ * gls_dist_create, both direct coarse solvers of the multigrid, and a non-zero
+ * value of gls_op_set_constraint_values on a Dirichlet component of a node
+ * with a row (the call then leaves the values set before untouched). */
+glsStatus gls_op_set_node_constraints(glsOp op, int64_t n, const int64_t *nodes,
+                                      const int32_t *comp, const double *coef, void *stream);
+/* number of rows and (n_colours may be NULL) of the colours the diagonal
+ * takes: compute_(inverse_)diagonal applies the operator dim * n_colours
+ * times to sums of unit vectors */
+glsStatus gls_op_n_node_constraints(glsOp op, int64_t *n, int *n_colours);
+/* AffineConstraints::distribute for what the operator knows, in place
+ * (main.cc:863, 968-969): Dirichlet components take 0 (homogeneous != 0) or
+ * the values of gls_op_set_constraint_values, then eliminated components
+ * take sum_e coef[e] u[node][e].  Honours gls_op_set_vector_layout. */
+glsStatus gls_op_distribute(glsOp op, void *vec, int homogeneous, void *stream);
 glsStatus gls_op_compute_inverse_diagonal(glsOp op, void *inv_diag,
                                           void *stream);
 /* OperatorBase::get_max_u (operator_base.h:71-72; NavierStokesOperator

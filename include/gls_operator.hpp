@@ -198,6 +198,34 @@ public:
     check(gls_op_set_constraint_values(h, values, stream), "set_constraint_values");
   }
 
+  // no-normal-flux rows on curved boundaries (main.cc:285-287):
+  // u[nodes[i]][comp[i]] = sum_e coef[i * dim + e] u[nodes[i]][e]; empty clears
+  void
+  set_node_constraints(const std::vector<int64_t> &nodes, const std::vector<int32_t> &comp,
+                       const std::vector<double> &coef, void *stream = nullptr)
+  {
+    if (comp.size() != nodes.size())
+      throw Error("set_node_constraints: nodes and comp differ in length");
+    check(gls_op_set_node_constraints(h, (int64_t)nodes.size(), nodes.data(), comp.data(),
+                                      coef.data(), stream),
+          "set_node_constraints");
+  }
+
+  int64_t
+  n_node_constraints(int *n_colours = nullptr) const
+  {
+    int64_t n = 0;
+    check(gls_op_n_node_constraints(h, &n, n_colours), "n_node_constraints");
+    return n;
+  }
+
+  // AffineConstraints::distribute in place (main.cc:863, 968-969)
+  void
+  distribute(void *vec, bool homogeneous = false, void *stream = nullptr) const
+  {
+    check(gls_op_distribute(h, vec, homogeneous ? 1 : 0, stream), "distribute");
+  }
+
   // operator_base.h:26-27 (operator_ns.cc:195-225)
   void
   compute_inverse_diagonal(void *diag, void *stream = nullptr) const
