@@ -26,7 +26,7 @@
 // transport), or every member of an in-process group on one device in
 // lockstep (n = world), as gls_dist_vmult / gls_dist_vmult_group.
 #include "../../include/gls_op.h"
-#include "cgs.h"
+#include "arnoldi.h"
 #include "common.h"
 #include "trace.h"
 #include "op_internal.h"
@@ -93,13 +93,6 @@ check(glsStatus st)
     throw std::runtime_error(gls_last_error());
 }
 
-void
-check_blas(rocblas_status st, const char *what)
-{
-  if (st != rocblas_status_success)
-    throw std::runtime_error(std::string(what) + ": rocBLAS status " + std::to_string((int)st));
-}
-
 // ---- kernels
 // part[block] = sum of a[i] b[i] over the block's rows (FP64)
 template <typename T>
@@ -158,16 +151,6 @@ k_mul(T *y, const T *d, int64_t n)
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n)
     y[i] *= d[i];
-}
-
-// t = b - t
-template <typename T>
-__global__ void
-k_rsub(T *t, const T *b, int64_t n)
-{
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n)
-    t[i] = b[i] - t[i];
 }
 
 template <typename Tin, typename Tout>
@@ -449,10 +432,10 @@ v_step(Team &t, int l, hipStream_t s)
       if (alone)
         ; // T already holds b - A x
       else if (x->prec == GLS_F64)
-        hipLaunchKernelGGL(k_rsub<double>, g1(n), dim3(256), 0, s, (double *)x->T[l],
+        hipLaunchKernelGGL(k_residual<double>, g1(n), dim3(256), 0, s, (double *)x->T[l],
                            (const double *)x->B[l], n);
       else
-        hipLaunchKernelGGL(k_rsub<float>, g1(n), dim3(256), 0, s, (float *)x->T[l],
+        hipLaunchKernelGGL(k_residual<float>, g1(n), dim3(256), 0, s, (float *)x->T[l],
                            (const float *)x->B[l], n);
       HIP_THROW(hipMemsetAsync(x->B[l - 1], 0, (size_t)x->n_dofs[(size_t)l - 1] * x->ts(), s));
       check(gls_mg_restrict_add(x->tr, l, x->B[l - 1], x->T[l], s));
@@ -962,11 +945,12 @@ gls_dist_mg_vcycle(glsDistMG const *team, int n, void *const *dst, const void *c
 // right-preconditioned GMRES(max_n_tmp_vectors - 2) with classical
 // Gram-Schmidt and one re-orthogonalisation; the basis in HBM, the dots over
 // the owned rows all-reduced (the Hessenberg column and |w|^2 cross to the
-// host together, once per iteration); x = 0 on entry.  As the single-domain
-// gls_gmres_solve: for up to 32 basis columns the orthogonalisation is the
-// fused CGS2 passes of cgs.h (all-reduces between them), v_{j+1} = w / |w|
-// is formed on the device, and Arnoldi step j + 1 is enqueued before the
-// host waits for step j's column (a converged solve runs one discarded step).  A: the FP64
+// host together, once per iteration); x = 0 on entry.  The restart loop and
+// the pipelined cycle are the single-domain solvers' (arnoldi.h: Arnoldi step
+// j + 1 is enqueued before the host waits for step j's column, a converged
+// solve runs one discarded step); the orthogonalisation is this solver's own:
+// for up to 32 basis columns the fused CGS2 passes of cgs.h per member with
+// all-reduces between them, v_{j+1} = w / |w| formed on the device.  A: the FP64
 // partitioned operator on the finest level's partition (the multigrid's
 // local vectors); mg NULL = identity preconditioner.
 glsStatus
@@ -1110,7 +1094,7 @@ gls_dist_gmres_solve(glsDist const *A, glsDistMG const *mg, int n, const glsGMRE
       HIP_THROW(hipMemsetAsync(x[r], 0, (size_t)ws[(size_t)r].nloc * 8, s));
       copy_vec(vcol(r, 0), b[r], (size_t)ws[(size_t)r].nloc * 8, s);
     }
-  std::vector<double> H((size_t)(m + 1) * m), g(m + 1), cs(m), sn(m), y(m);
+  std::vector<double> col((size_t)m + 1);
   // the Hessenberg column h1 | h2 | |w|^2 of member 0 (all-reduced) to
   // pinned host memory, double-buffered by step parity
   const int64_t HC = 2 * (m + 1) + 1;
@@ -1205,11 +1189,9 @@ gls_dist_gmres_solve(glsDist const *A, glsDistMG const *mg, int n, const glsGMRE
                          (const double *)(ws[(size_t)r].h + 2 * (m + 1)), ws[(size_t)r].nloc);
     HIP_THROW(hipGetLastError());
   };
-  int    it = 0, n_rst = 0;
-  double res = bnorm;
-  while (res > tol && it < desc->max_iterations)
-    {
-      const double sc = 1.0 / res;
+  gls::GmresSpace sp{
+    [&](double beta) {
+      const double sc = 1.0 / beta;
       for (int r = 0; r < n; ++r)
         {
           rocblas_set_pointer_mode(h, rocblas_pointer_mode_host);
@@ -1217,56 +1199,22 @@ gls_dist_gmres_solve(glsDist const *A, glsDistMG const *mg, int n, const glsGMRE
                      "rocblas_dscal");
           rocblas_set_pointer_mode(h, rocblas_pointer_mode_device);
         }
-      std::fill(H.begin(), H.end(), 0.0);
-      std::fill(g.begin(), g.end(), 0.0);
-      g[0]   = res;
-      int jd = 0;
-      if (m > 0)
-        arnoldi(0);
-      for (int j = 0; j < m && it < desc->max_iterations; ++j)
-        {
-          // step j + 1 in flight while the host handles step j
-          if (j + 1 < m && it + 1 < desc->max_iterations)
-            arnoldi(j + 1);
-          HIP_THROW(hipEventSynchronize(pin.e[j % 2]));
-          const double *hc = pin.p + (j % 2) * HC;
-          double       *Hj = &H[(size_t)j * (m + 1)];
-          for (int i = 0; i <= j; ++i)
-            Hj[i] = hc[(size_t)i] + hc[(size_t)(m + 1 + i)];
-          const double hn = std::sqrt(std::max(0.0, hc[(size_t)(2 * (m + 1))]));
-          Hj[j + 1]       = hn;
-          for (int i = 0; i < j; ++i)
-            {
-              const double tt = cs[(size_t)i] * Hj[i] + sn[(size_t)i] * Hj[i + 1];
-              Hj[i + 1]       = -sn[(size_t)i] * Hj[i] + cs[(size_t)i] * Hj[i + 1];
-              Hj[i]           = tt;
-            }
-          const double rr = std::hypot(Hj[j], Hj[j + 1]);
-          cs[(size_t)j]   = rr > 0 ? Hj[j] / rr : 1.0;
-          sn[(size_t)j]   = rr > 0 ? Hj[j + 1] / rr : 0.0;
-          Hj[j]           = rr;
-          Hj[j + 1]       = 0;
-          g[(size_t)j + 1] = -sn[(size_t)j] * g[(size_t)j];
-          g[(size_t)j]     = cs[(size_t)j] * g[(size_t)j];
-          ++it;
-          ++jd;
-          res = std::fabs(g[(size_t)j + 1]);
-          if (res <= tol || hn == 0)
-            break;
-        }
+    },
+    arnoldi,
+    // step j's column; |w|^2 was all-reduced, the root is taken here
+    [&](int j) {
+      HIP_THROW(hipEventSynchronize(pin.e[j % 2]));
+      cgs2_column(pin.p + (j % 2) * HC, m, j, col.data());
+      col[(size_t)j + 1] = std::sqrt(std::max(0.0, col[(size_t)j + 1]));
+      return (const double *)col.data();
+    },
+    // x += P (V y)
+    [&](int jd, const double *y) {
       // the discarded step (if any) has finished before its columns are reused
       HIP_THROW(hipStreamSynchronize(s));
-      for (int i = jd - 1; i >= 0; --i)
-        {
-          double tt = g[(size_t)i];
-          for (int c = i + 1; c < jd; ++c)
-            tt -= H[(size_t)c * (m + 1) + i] * y[(size_t)c];
-          y[(size_t)i] = tt / H[(size_t)i * (m + 1) + i];
-        }
-      // x += P (V y)
       for (int r = 0; r < n; ++r)
         {
-          HIP_THROW(hipMemcpyAsync(ws[(size_t)r].h, y.data(), jd * 8, hipMemcpyHostToDevice, s));
+          HIP_THROW(hipMemcpyAsync(ws[(size_t)r].h, y, jd * 8, hipMemcpyHostToDevice, s));
           check_blas(rocblas_dgemv(h, rocblas_operation_none, (rocblas_int)ws[(size_t)r].nloc, jd,
                                    d_c, ws[(size_t)r].V, (rocblas_int)ws[(size_t)r].nloc,
                                    ws[(size_t)r].h, 1, d_c + 2, ws[(size_t)r].w, 1),
@@ -1280,38 +1228,37 @@ gls_dist_gmres_solve(glsDist const *A, glsDistMG const *mg, int n, const glsGMRE
                    "rocblas_daxpy");
       rocblas_set_pointer_mode(h, rocblas_pointer_mode_device);
       HIP_THROW(hipStreamSynchronize(s)); // y is reused
-      if (res <= tol || it >= desc->max_iterations)
-        break;
-      // restart: V_0 = b - A x
+    },
+    // restart: V_0 = b - A x
+    [&] {
       apply_A(V0, Xv);
       rocblas_set_pointer_mode(h, rocblas_pointer_mode_host);
       for (int r = 0; r < n; ++r)
         {
-          const double m1 = -1.0;
-          check_blas(rocblas_dscal(h, (rocblas_int)ws[(size_t)r].nloc, &m1, vcol(r, 0), 1),
+          check_blas(rocblas_dscal(h, (rocblas_int)ws[(size_t)r].nloc, &mone, vcol(r, 0), 1),
                      "rocblas_dscal");
           check_blas(rocblas_daxpy(h, (rocblas_int)ws[(size_t)r].nloc, &one, (const double *)b[r],
                                    1, vcol(r, 0), 1),
                      "rocblas_daxpy");
         }
       rocblas_set_pointer_mode(h, rocblas_pointer_mode_device);
-      res = norm(V0);
-      ++n_rst;
-    }
+      return norm(V0);
+    }};
+  const gls::GmresRun run = gls::gmres_restarted(sp, m, bnorm, tol, desc->max_iterations);
   HIP_THROW(hipFreeAsync(d_c, s));
   HIP_THROW(hipStreamSynchronize(s));
   if (result)
     {
-      result->n_iterations     = it;
-      result->n_restarts       = n_rst;
-      result->converged        = res <= tol;
+      result->n_iterations     = run.iterations;
+      result->n_restarts       = run.restarts;
+      result->converged        = run.converged;
       result->initial_residual = bnorm;
-      result->final_residual   = res;
+      result->final_residual   = run.residual;
       result->tolerance        = tol;
     }
-  if (res > tol)
+  if (!run.converged)
     {
-      gls::set_error("gls_dist_gmres_solve: no convergence in " + std::to_string(it) +
+      gls::set_error("gls_dist_gmres_solve: no convergence in " + std::to_string(run.iterations) +
                      " iterations (SolverControl::NoConvergence)");
       return 1;
     }

@@ -16,7 +16,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "op_internal.h"
-#include "cgs.h"
+#include "arnoldi.h"
 #include "coarse_nd_solver.h"
 #include "trace.h"
 
@@ -436,16 +436,6 @@ k_relax_first(T *__restrict__ x, const T *__restrict__ b, const T *__restrict__ 
   else
     bi = b[i];
   x[i] = omega * d[i] * bi;
-}
-
-// t = b - t  (Multigrid residual step)
-template <typename T>
-__global__ void
-k_residual(T *__restrict__ t, const T *__restrict__ b, int64_t n)
-{
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n)
-    t[i] = b[i] - t[i];
 }
 
 // zero fill / copy of the V-cycle's own buffers (kernels)
@@ -1064,14 +1054,6 @@ residual(const glsMG_ *mg, int level, void *t, const void *b, hipStream_t s)
     hipLaunchKernelGGL(k_residual<float>, g1(n), dim3(256), 0, s, (float *)t,
                        (const float *)b, n);
   HIP_THROW(hipGetLastError());
-}
-
-void
-check_blas(rocblas_status st, const char *what)
-{
-  if (st != rocblas_status_success)
-    throw std::runtime_error(std::string(what) + " failed (rocblas status " +
-                             std::to_string((int)st) + ")");
 }
 
 // X = the unit lower triangle of the LU factors (column major n x n):
@@ -2183,15 +2165,6 @@ coarse_apply(glsMG_ *mg, hipStream_t s, PendingReduce *pend = nullptr)
            pend);
 }
 
-// r = b - r (the coarse GMRES restart residual)
-__global__ void
-k_sub(double *__restrict__ r, const double *__restrict__ b, int64_t n)
-{
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n)
-    r[i] = b[i] - r[i];
-}
-
 // coarse_grid_iterate (multigrid.cc:491-530, MGCoarseGridIterativeSolver):
 // SolverGMRES<VectorType<double>> with deal.II's defaults (left
 // preconditioning, max_n_tmp_vectors 30 -> restart after 28) under
@@ -2200,11 +2173,11 @@ k_sub(double *__restrict__ r, const double *__restrict__ b, int64_t n)
 // relaxation sweeps or the dense LU).  FP64 Krylov vectors, the level
 // operator and preconditioner in the level precision (the reference solves
 // with the FP64 system matrix assembled from the MGNumber operator).  Every
-// vector stays on the device.  The Arnoldi step runs as the outer solver's
-// (krylov.hip): fused CGS2 passes (cgs.h), |w| and v_{j+1} = w / |w| on the
-// device, and step j + 1 enqueued before the host waits for step j's
-// Hessenberg column (pinned, double-buffered), so the device never idles
-// through the host round trip; a converged solve runs one discarded step.
+// vector stays on the device.  The restart loop, the pipelined cycle (step
+// j + 1 enqueued before the host waits for step j's Hessenberg column,
+// pinned and double-buffered; a converged solve runs one discarded step) and
+// the CGS2 step are the shared ones of arnoldi.h, as in the outer solver
+// (krylov.hip); the lambdas below are their space.
 template <typename T>
 void
 coarse_gmres_t(glsMG_ *mg, hipStream_t s)
@@ -2289,137 +2262,47 @@ coarse_gmres_t(glsMG_ *mg, hipStream_t s)
     apply_A(w, vc(j));
     double *wv = vc(j + 1);
     prec(wv, w);
-    double *hn = dh + 2 * (m + 1);
-    const int J         = j + 1;
-    bool      unit_done = false;
-    if (J < CGS_MAXJ)
-      {
-        // CGS2 with the second update folded into the normalisation
-        // (krylov.hip, cgs.h k_cgs_unit)
-        hipLaunchKernelGGL(k_cgs_dots, dim3(CGS_BLOCKS), dim3(256), 0, s, (const double *)V, J,
-                           (const double *)wv, cpart, n, n);
-        hipLaunchKernelGGL(k_cgs_finish, dim3(J), dim3(256), 0, s, (const double *)cpart, dh, 0);
-        hipLaunchKernelGGL(k_cgs_update, dim3(CGS_BLOCKS), dim3(256), 0, s, (const double *)V, J,
-                           (const double *)dh, wv, cpart, n, n, n, 2);
-        hipLaunchKernelGGL(k_cgs_finish, dim3(J + 1), dim3(256), 0, s, (const double *)cpart,
-                           dh + (m + 1), 0);
-        hipLaunchKernelGGL(k_cgs_unit, dim3(CGS_BLOCKS), dim3(256), 0, s, (const double *)V, J,
-                           (const double *)(dh + (m + 1)), (const double *)wv, wv, hn, n, n,
-                           (const double *)dh, host_dev + (j % 2) * HC, HC, 2 * (m + 1));
-        HIP_THROW(hipGetLastError());
-        unit_done = true;
-      }
-    else if (J <= CGS_MAXJ)
-      {
-        hipLaunchKernelGGL(k_cgs_dots, dim3(CGS_BLOCKS), dim3(256), 0, s, (const double *)V, J,
-                           (const double *)wv, cpart, n, n);
-        hipLaunchKernelGGL(k_cgs_finish, dim3(J), dim3(256), 0, s, (const double *)cpart, dh, 0);
-        hipLaunchKernelGGL(k_cgs_update, dim3(CGS_BLOCKS), dim3(256), 0, s, (const double *)V, J,
-                           (const double *)dh, wv, cpart, n, n, n, 0);
-        hipLaunchKernelGGL(k_cgs_finish, dim3(J), dim3(256), 0, s, (const double *)cpart,
-                           dh + (m + 1), 0);
-        hipLaunchKernelGGL(k_cgs_update, dim3(CGS_BLOCKS), dim3(256), 0, s, (const double *)V, J,
-                           (const double *)(dh + (m + 1)), wv, cpart, n, n, n, 1);
-        hipLaunchKernelGGL(k_cgs_finish, dim3(1), dim3(256), 0, s, (const double *)cpart, hn, 1);
-        HIP_THROW(hipGetLastError());
-      }
-    else
-      {
-        const double one = 1.0, zero = 0.0, mone = -1.0;
-        for (int pass = 0; pass < 2; ++pass)
-          {
-            double *hp = dh + pass * (m + 1);
-            check_blas(rocblas_dgemv(h, rocblas_operation_transpose, (rocblas_int)n, J, &one, V,
-                                     (rocblas_int)n, wv, 1, &zero, hp, 1),
-                       "rocblas_dgemv");
-            check_blas(rocblas_dgemv(h, rocblas_operation_none, (rocblas_int)n, J, &mone, V,
-                                     (rocblas_int)n, hp, 1, &one, wv, 1),
-                       "rocblas_dgemv");
-          }
-        check_blas(rocblas_set_pointer_mode(h, rocblas_pointer_mode_device), "pointer mode");
-        check_blas(rocblas_dnrm2(h, (rocblas_int)n, wv, 1, hn), "rocblas_dnrm2");
-        check_blas(rocblas_set_pointer_mode(h, rocblas_pointer_mode_host), "pointer mode");
-      }
-    if (!unit_done)
-      HIP_THROW(hipMemcpyAsync(mg->cg_host + (j % 2) * HC, dh, HC * 8, hipMemcpyDeviceToHost, s));
-    HIP_THROW(hipEventRecord(mg->cg_ev[j % 2], s));
-    if (!unit_done)
-      hipLaunchKernelGGL(k_unit_col, g1(n), dim3(256), 0, s, wv, (const double *)wv,
-                         (const double *)hn, n);
-    HIP_THROW(hipGetLastError());
+    cgs2_step(V, n, wv, wv, dh, cpart, mg->cg_host + (j % 2) * HC, host_dev + (j % 2) * HC, HC, m,
+              j, h, s, mg->cg_ev[j % 2], false, false);
   };
   cvt_out(b, (const T *)mg->def[0]);
   HIP_THROW(hipMemsetAsync(x, 0, n * 8, s));
   // r0 = P^{-1} (b - A 0)
   prec(vc(0), b);
-  double       res = nrm2(vc(0));
-  const double tol = std::max(mg->desc.coarse_reltol * res, 1e-20);
-  int          it  = 0;
-  std::vector<double> H((size_t)(m + 1) * m), g(m + 1), cs(m), sn(m), y(m);
-  while (res > tol && it < mg->desc.coarse_maxiter)
-    {
-      const double sc = 1.0 / res;
+  const double res0 = nrm2(vc(0));
+  const double tol  = std::max(mg->desc.coarse_reltol * res0, 1e-20);
+  double       col[m + 1];
+  gls::GmresSpace sp{
+    [&](double beta) {
+      const double sc = 1.0 / beta;
       check_blas(rocblas_dscal(h, (rocblas_int)n, &sc, vc(0), 1), "rocblas_dscal");
-      std::fill(g.begin(), g.end(), 0.0);
-      g[0]   = res;
-      int jd = 0;
-      arnoldi(0);
-      for (int j = 0; j < m && it < mg->desc.coarse_maxiter; ++j)
-        {
-          if (j + 1 < m && it + 1 < mg->desc.coarse_maxiter)
-            arnoldi(j + 1);
-          HIP_THROW(hipEventSynchronize(mg->cg_ev[j % 2]));
-          const double *hc = mg->cg_host + (j % 2) * HC;
-          const double  hn = hc[2 * (m + 1)];
-          double       *Hj = &H[(size_t)j * (m + 1)];
-          for (int i = 0; i <= j; ++i)
-            Hj[i] = hc[i] + hc[(m + 1) + i];
-          Hj[j + 1] = hn;
-          for (int i = 0; i < j; ++i)
-            {
-              const double t = cs[i] * Hj[i] + sn[i] * Hj[i + 1];
-              Hj[i + 1]      = -sn[i] * Hj[i] + cs[i] * Hj[i + 1];
-              Hj[i]          = t;
-            }
-          const double rr = std::hypot(Hj[j], Hj[j + 1]);
-          cs[j]           = rr > 0 ? Hj[j] / rr : 1.0;
-          sn[j]           = rr > 0 ? Hj[j + 1] / rr : 0.0;
-          Hj[j]           = rr;
-          Hj[j + 1]       = 0;
-          g[j + 1]        = -sn[j] * g[j];
-          g[j]            = cs[j] * g[j];
-          ++it;
-          ++jd;
-          res = std::fabs(g[j + 1]);
-          if (res <= tol || hn == 0)
-            break;
-        }
-      // x += V y (left preconditioning: the update is in the Krylov space)
-      for (int i = jd - 1; i >= 0; --i)
-        {
-          double t = g[i];
-          for (int c = i + 1; c < jd; ++c)
-            t -= H[(size_t)c * (m + 1) + i] * y[c];
-          y[i] = t / H[(size_t)i * (m + 1) + i];
-        }
-      HIP_THROW(hipMemcpyAsync(dh, y.data(), jd * 8, hipMemcpyHostToDevice, s));
-      {
-        const double one = 1.0;
-        check_blas(rocblas_dgemv(h, rocblas_operation_none, (rocblas_int)n, jd, &one, V,
-                                 (rocblas_int)n, dh, 1, &one, x, 1),
-                   "rocblas_dgemv");
-      }
-      HIP_THROW(hipStreamSynchronize(s)); // y is a host buffer reused below
-      if (res <= tol || it >= mg->desc.coarse_maxiter)
-        break;
-      // restart: r = P^{-1} (b - A x)
+    },
+    arnoldi,
+    [&](int j) {
+      HIP_THROW(hipEventSynchronize(mg->cg_ev[j % 2]));
+      return cgs2_column(mg->cg_host + (j % 2) * HC, m, j, col);
+    },
+    // x += V y (left preconditioning: the update is in the Krylov space)
+    [&](int jd, const double *y) {
+      HIP_THROW(hipMemcpyAsync(dh, y, jd * 8, hipMemcpyHostToDevice, s));
+      const double one = 1.0;
+      check_blas(rocblas_dgemv(h, rocblas_operation_none, (rocblas_int)n, jd, &one, V,
+                               (rocblas_int)n, dh, 1, &one, x, 1),
+                 "rocblas_dgemv");
+      HIP_THROW(hipStreamSynchronize(s)); // y is a host buffer reused by the next cycle
+    },
+    // restart: r = P^{-1} (b - A x)
+    [&] {
       apply_A(w, x);
-      hipLaunchKernelGGL(k_sub, g1(n), dim3(256), 0, s, w, b, n);
+      hipLaunchKernelGGL(k_residual<double>, g1(n), dim3(256), 0, s, w, (const double *)b, n);
       prec(vc(0), w);
-      res = nrm2(vc(0));
-    }
+      return nrm2(vc(0));
+    }};
+  const gls::GmresRun run = gls::gmres_restarted(sp, m, res0, tol, mg->desc.coarse_maxiter);
+  const int           it  = run.iterations;
+  const double        res = run.residual;
   mg->cg_iters = it;
-  mg->cg_conv  = res <= tol;
+  mg->cg_conv  = run.converged;
   // deal.II's SolverGMRES inside MGCoarseGridIterativeSolver throws
   // SolverControl::NoConvergence when maxiter is reached (multigrid.cc:
   // 494-530): the V-cycle fails the same way instead of continuing with an
