@@ -603,6 +603,10 @@ gls_dist_create(glsOp op, const glsDistDesc *desc, glsDist *out)
   if (op->nc.n)
     throw std::runtime_error("gls_dist_create: node constraints are single-domain only "
                              "(partitioned operators with node constraints are not supported)");
+  if (!op->h_master.empty())
+    throw std::runtime_error("gls_dist_create: a periodic node map (node_master) is "
+                             "single-domain only (partitioned operators with one are not "
+                             "supported)");
   if (desc->world < 1 || desc->rank < 0 || desc->rank >= desc->world)
     throw std::runtime_error("gls_dist_create: bad rank / world");
   HIP_THROW(hipSetDevice(op->device));

@@ -522,7 +522,7 @@ gls_op_set_force_faces(glsOp op, int64_t n_faces, const int64_t *cells, const in
       cell[(size_t)f] = internal[(size_t)cells[f]];
       for (int i = 0; i < nq; ++i)
         {
-          const size_t node = op->h_cell_nodes[(size_t)cells[f] * nq + i];
+          const size_t node = op->geo_nodes()[(size_t)cells[f] * nq + i];
           for (int d = 0; d < dim; ++d)
             xc[((size_t)f * nq + i) * dim + d] = node_coords[node * dim + d];
         }
@@ -587,7 +587,7 @@ gls_op_set_probe_points(glsOp op, int64_t n_points, const double *xyz, const dou
     throw std::runtime_error("gls_op_set_probe_points: bad arguments");
   gls::check_geometry(op, "gls_op_set_probe_points");
   gls::ProbePairs pairs;
-  gls::locate_points(op->dim, op->degree, op->n_cells, op->h_cell_nodes.data(), op->n_nodes,
+  gls::locate_points(op->dim, op->degree, op->n_cells, op->geo_nodes().data(), op->n_nodes,
                      node_coords, n_points, xyz, pairs);
   gls::DeviceScope dev(op->device);
   gls::Forces     &F = op->forces;

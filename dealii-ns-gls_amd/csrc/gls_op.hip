@@ -336,19 +336,22 @@ build_bricks(glsOp_ *op, const glsOpDesc *d, const char *cell_curved)
                                        "(shared lattice nodes differ)");
           }
       }
-  // brick multiplicity of each node
+  // brick multiplicity of each node: its lattice positions over all bricks.
+  // A node holds one position per brick, except under a periodic node map
+  // (glsOpDesc.node_master) whose period is the brick's extent: the brick
+  // then holds the node at two positions, each with a partial slot of its own
+  // (the node is shared)
   std::vector<uint32_t> mult((size_t)d->n_nodes, 0), last((size_t)d->n_nodes, UINT32_MAX);
+  bool                  twice = false;
   for (int64_t b = 0; b < nb; ++b)
     for (int i = 0; i < L; ++i)
       {
         const uint32_t node = bnodes[(size_t)b * L + i];
         if (node == UINT32_MAX)
           continue;
-        if (last[node] != (uint32_t)b)
-          {
-            last[node] = (uint32_t)b;
-            mult[node]++;
-          }
+        twice      = twice || last[node] == (uint32_t)b;
+        last[node] = (uint32_t)b;
+        mult[node]++;
       }
   // targets: exclusive owned nodes -> node id; every other node is "shared":
   // its per-brick partials occupy a contiguous slot range [off[s], off[s+1])
@@ -422,7 +425,7 @@ build_bricks(glsOp_ *op, const glsOpDesc *d, const char *cell_curved)
   std::vector<uint32_t> fill(shared_nodes.size(), 0);
   for (int64_t b = 0; b < nb; ++b)
     {
-      // a node appears once per brick lattice
+      // one slot per lattice position
       for (int i = 0; i < L; ++i)
         {
           const uint32_t node = bnodes[(size_t)b * L + i];
@@ -447,7 +450,7 @@ build_bricks(glsOp_ *op, const glsOpDesc *d, const char *cell_curved)
     for (uint32_t node : shared_nodes)
       max_mult = std::max(max_mult, mult[node]);
     if (op->prec == GLS_F32 && dim == 3 && k == 2 && nb <= 4096 && n_slot_total > 0 &&
-        L <= SWEEP_MAX_L &&
+        L <= SWEEP_MAX_L && !twice && // (a resident brick waits for the other bricks' slots only)
         max_mult <= (uint32_t)SWEEP_MAX_MULT && n_slot_total * 32 < (1ull << 31))
       {
         for (auto &g : op->d_sweep_gran)
@@ -1730,6 +1733,67 @@ gls_op_create(const glsOpDesc *d, glsOp *out)
         }
     }
   d = &dd;
+  // periodic node identification (glsOpDesc.node_master): geo_nodes, the
+  // caller's connectivity, for everything that reads coordinates; a_nodes,
+  // mapped through node_master, for every vector or matrix entry.  The slaves
+  // are in no cell of a_nodes and fully constrained; the master takes the OR of
+  // its group's mask.
+  const uint32_t       *geo_nodes = d->cell_nodes; // internal cell order
+  std::vector<uint32_t> a_nodes;
+  std::vector<uint8_t>  a_cmask;
+  std::vector<int64_t>  slaves;
+  if (d->node_master)
+    {
+      const int nqc = d->dim == 3 ? (d->degree + 1) * (d->degree + 1) * (d->degree + 1)
+                                  : (d->degree + 1) * (d->degree + 1);
+      if (d->n_owned_nodes != d->n_nodes)
+        throw std::runtime_error("gls_op_create: node_master on a partitioned operator is not "
+                                 "supported (owned nodes only)");
+      if (d->mapping_points)
+        throw std::runtime_error("gls_op_create: node_master with mapping_points (an "
+                                 "FE_Q_iso_Q1 level) is not supported");
+      const int64_t *nm = d->node_master;
+      for (int64_t i = 0; i < d->n_nodes; ++i)
+        {
+          if (nm[i] < 0 || nm[i] >= d->n_nodes)
+            throw std::runtime_error("gls_op_create: node_master[" + std::to_string(i) +
+                                     "] out of range");
+          if (nm[nm[i]] != nm[i])
+            throw std::runtime_error("gls_op_create: node_master is not idempotent at node " +
+                                     std::to_string(i) + " (its master is a slave)");
+        }
+      const uint8_t all = (uint8_t)((1u << (d->dim + 1)) - 1u);
+      a_cmask.assign(d->node_cmask, d->node_cmask + d->n_nodes);
+      for (int64_t i = 0; i < d->n_nodes; ++i)
+        if (nm[i] != i)
+          {
+            a_cmask[(size_t)nm[i]] |= (uint8_t)(d->node_cmask[i] & all);
+            slaves.push_back(i);
+          }
+      for (int64_t i : slaves)
+        a_cmask[(size_t)i] = all;
+      a_nodes.resize((size_t)d->n_cells * nqc);
+      for (int64_t c = 0; c < d->n_cells; ++c)
+        {
+          for (int p = 0; p < nqc; ++p)
+            {
+              const uint32_t g = geo_nodes[c * nqc + p];
+              if ((int64_t)g >= d->n_nodes)
+                throw std::runtime_error("gls_op_create: node index out of range");
+              a_nodes[(size_t)(c * nqc + p)] = (uint32_t)nm[g];
+            }
+          for (int p = 0; p < nqc; ++p)
+            for (int q = 0; q < p; ++q)
+              if (a_nodes[(size_t)(c * nqc + p)] == a_nodes[(size_t)(c * nqc + q)])
+                throw std::runtime_error(
+                  "gls_op_create: cell " +
+                  std::to_string(p_nodes.empty() ? c : plan.perm[(size_t)c]) +
+                  " lists node " + std::to_string(a_nodes[(size_t)(c * nqc + p)]) +
+                  " twice under node_master (a period of one cell is not supported)");
+        }
+      dd.cell_nodes = a_nodes.data();
+      dd.node_cmask = a_cmask.data();
+    }
   auto *op          = new glsOp_();
   // an invalid descriptor found below (bricks, outflow faces, allocation
   // failures) frees what was built so far
@@ -1774,6 +1838,22 @@ gls_op_create(const glsOpDesc *d, glsOp *out)
   upload((void **)&op->d_nodes, nodes);
   op->h_cmask.assign(d->node_cmask, d->node_cmask + d->n_nodes);
   op->h_cell_nodes.assign(caller->cell_nodes, caller->cell_nodes + (size_t)d->n_cells * nq);
+  if (d->node_master)
+    {
+      // h_cell_nodes is the algebraic connectivity, h_geo_nodes the caller's
+      op->h_geo_nodes = op->h_cell_nodes;
+      for (uint32_t &v : op->h_cell_nodes)
+        v = (uint32_t)d->node_master[v];
+      op->h_master.assign(d->node_master, d->node_master + d->n_nodes);
+      op->n_slaves = (int64_t)slaves.size();
+      std::vector<int64_t> pairs(2 * slaves.size());
+      for (size_t i = 0; i < slaves.size(); ++i)
+        {
+          pairs[2 * i]     = slaves[i];
+          pairs[2 * i + 1] = d->node_master[slaves[i]];
+        }
+      upload((void **)&op->d_slave_pairs, pairs);
+    }
 
   // constrained dof bitmask on the owned range (identity rows)
   std::vector<uint32_t> cbits((size_t)(op->n_owned_dofs + 31) / 32 + 1, 0u);
@@ -1808,7 +1888,7 @@ gls_op_create(const glsOpDesc *d, glsOp *out)
         {
           for (int i = 0; i < nq; ++i)
             for (int e = 0; e < dim; ++e)
-              X[i * dim + e] = d->node_coords[(size_t)d->cell_nodes[c * nq + i] * dim + e];
+              X[i * dim + e] = d->node_coords[(size_t)geo_nodes[c * nq + i] * dim + e];
           cell_jacobians(dim, op->basis, X.data(), J);
         }
       double scale = 0;
@@ -2006,7 +2086,7 @@ gls_op_destroy(glsOp op)
                   op->d_brick_rec,    op->d_coef_image,   op->d_tab_cbase,
                   op->d_node_cmask,   op->d_inhom,        op->gmres_ws,
                   op->d_colour_cells, op->d_sweep_gran[0], op->d_sweep_gran[1],
-                  op->d_sweep_err};
+                  op->d_sweep_err,    op->d_slave_pairs};
   for (void *b : bufs)
     if (b)
       (void)hipFree(b);

@@ -1662,6 +1662,9 @@ coarse_lu_setup_t(glsMG_ *mg, hipStream_t s)
   // (the nested-dissection solver checks the free device memory instead)
   const bool nd = mg->coarse_method == GLS_COARSE_ND && !mg->nd_failed &&
                   !coarse_reference("columns");
+  if (nd && !op->h_master.empty())
+    throw std::runtime_error("the \"nd\" coarse solver does not take a coarse level with a "
+                             "periodic node map (node_master); use the dense direct solver");
   if (n > 40000 && !nd)
     throw std::runtime_error("dense LU coarse solver: coarse level too large");
   std::vector<int32_t> freel;
@@ -2592,6 +2595,17 @@ gls_mg_create(const glsMGDesc *desc, const glsOp *levels, const uint32_t *const 
       const int     nl  = mg->dim == 3 ? L * L * L : L * L;
       const int64_t nch = cop->n_cells * nl;
       std::vector<uint32_t> ch(child[l], child[l] + nch);
+      // a periodic node map of the fine level (glsOpDesc.node_master): the
+      // lattices address unknowns, so they go through it before ownership and
+      // weights are assigned (no coarse cell's lattice holds a node twice: the
+      // coarse operator refused a cell that lists one twice)
+      if (!fop->h_master.empty())
+        for (uint32_t &fn : ch)
+          {
+            if ((int64_t)(fn & ~NOT_OWNER) >= fop->n_nodes)
+              throw std::runtime_error("gls_mg_create: child lattice node out of range");
+            fn = (uint32_t)fop->h_master[fn & ~NOT_OWNER] | (fn & NOT_OWNER);
+          }
       std::vector<uint8_t>  seen((size_t)fop->n_nodes, 0);
       // ownership of the fine nodes: the first coarse cell touching a node
       // owns it; a lattice that already carries NOT_OWNER bits (bit 31,

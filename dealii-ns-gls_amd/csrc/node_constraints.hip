@@ -114,6 +114,22 @@ __global__ void __launch_bounds__(NC_BLOCK)
     v[i] = inhom ? inhom[i] : T(0);
 }
 
+// AffineConstraints::distribute for a periodic node map: one lane per slave
+// entry, v[slave][c] <- v[master][c] (pairs: [n][2] slave node, master node;
+// a master is no slave, so no lane reads what another writes)
+template <typename T>
+__global__ void __launch_bounds__(NC_BLOCK)
+  k_periodic_resolve(T *__restrict__ v, const int64_t *__restrict__ pairs, int64_t n_entries,
+                     int nc)
+{
+  const int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (t >= n_entries)
+    return;
+  const int64_t r = t / nc;
+  const int     c = (int)(t - r * nc);
+  v[pairs[2 * r] * nc + c] = v[pairs[2 * r + 1] * nc + c];
+}
+
 // the colour's unit vectors of component j: unit[node][j] <- value
 template <typename T>
 __global__ void __launch_bounds__(NC_BLOCK)
@@ -570,6 +586,10 @@ gls_op_set_node_constraints(glsOp op, int64_t n, const int64_t *nodes, const int
       if (comp[i] < 0 || comp[i] >= dim)
         throw std::runtime_error("gls_op_set_node_constraints: comp must be a velocity "
                                  "component" + at);
+      if (!op->h_master.empty() && op->h_master[(size_t)nodes[i]] != nodes[i])
+        throw std::runtime_error("gls_op_set_node_constraints: node " +
+                                 std::to_string(nodes[i]) + " is a slave of the periodic node "
+                                 "map (its row belongs to its master)" + at);
       const unsigned mask = op->h_cmask[(size_t)nodes[i]];
       if ((mask >> comp[i]) & 1)
         throw std::runtime_error("gls_op_set_node_constraints: comp is in the node's Dirichlet "
@@ -679,6 +699,18 @@ gls_op_distribute(glsOp op, void *vec, int homogeneous, void *stream)
       HIP_THROW(hipGetLastError());
     }
   nc_resolve(op, v, false, s);
+  // periodic node map: slave := master, after the masters took their values
+  if (op->n_slaves > 0)
+    {
+      const int64_t n = op->n_slaves * (op->dim + 1);
+      if (op->prec == GLS_F64)
+        hipLaunchKernelGGL(k_periodic_resolve<double>, nc_grid(n), dim3(NC_BLOCK), 0, s,
+                           (double *)v, op->d_slave_pairs, n, op->dim + 1);
+      else
+        hipLaunchKernelGGL(k_periodic_resolve<float>, nc_grid(n), dim3(NC_BLOCK), 0, s,
+                           (float *)v, op->d_slave_pairs, n, op->dim + 1);
+      HIP_THROW(hipGetLastError());
+    }
   op->stage.finish_out(vec, s);
   op->stage.done(s);
   GLS_CATCH

@@ -149,9 +149,25 @@ struct glsOp_
   // host copies the multigrid transfer setup needs
   std::vector<uint8_t>  h_cmask;      // [n_nodes]
   std::vector<uint32_t> h_cell_nodes; // [n_cells][nq], caller cell order
+  // periodic node map (glsOpDesc.node_master; empty: none).  With one,
+  // h_cell_nodes is the algebraic connectivity (mapped through h_master: no
+  // slave in it) and h_cmask the mask with the masters' OR-ed bits and all
+  // bits on the slaves; h_geo_nodes keeps the caller's connectivity for what
+  // reads coordinates (force faces, point location)
+  std::vector<int64_t>  h_master;    // [n_nodes]
+  std::vector<uint32_t> h_geo_nodes; // [n_cells][nq], caller cell order
+  int64_t               n_slaves      = 0;
+  int64_t              *d_slave_pairs = nullptr; // [n_slaves][2] slave node, master node
   // discovered bricks (glsOpDesc::brick[0] < 0): the operator runs its cells
   // in brick order, cell_perm[internal cell] = caller cell (empty: identity)
   std::vector<int64_t>  cell_perm;
+
+  // the connectivity that goes with node coordinates
+  const std::vector<uint32_t> &
+  geo_nodes() const
+  {
+    return h_geo_nodes.empty() ? h_cell_nodes : h_geo_nodes;
+  }
 
   int64_t n_gen = 0, n_cart = 0;
   // device buffers

@@ -1261,6 +1261,136 @@ gls_mesh_nonplanar_ids(const glsMesh *m)
 }
 
 int
+gls_mesh_periodic_nodes(const glsMesh *m, int n_pairs, const int32_t *id_a, const int32_t *id_b,
+                        const int32_t *direction, int64_t *node_master)
+{
+  if (!m || n_pairs < 0 || !node_master || (n_pairs > 0 && (!id_a || !id_b || !direction)))
+    {
+      g_err = "gls_mesh_periodic_nodes: bad argument";
+      return 1;
+    }
+  const int     dim = m->dim;
+  const int64_t nn  = m->n_nodes;
+  for (int64_t i = 0; i < nn; ++i)
+    node_master[i] = i;
+  // tolerance: 1e-9 x the mesh extent
+  double extent = 0;
+  for (int d = 0; d < dim; ++d)
+    {
+      double lo = DBL_MAX, hi = -DBL_MAX;
+      for (int64_t i = 0; i < nn; ++i)
+        {
+          lo = std::min(lo, m->coords[(size_t)i * dim + d]);
+          hi = std::max(hi, m->coords[(size_t)i * dim + d]);
+        }
+      if (nn > 0)
+        extent = std::max(extent, hi - lo);
+    }
+  const double tol = 1e-9 * extent;
+  for (int p = 0; p < n_pairs; ++p)
+    {
+      const std::string at = " (pair " + std::to_string(p) + ")";
+      if (id_a[p] < 0 || id_a[p] > 31 || id_b[p] < 0 || id_b[p] > 31 || id_a[p] == id_b[p])
+        {
+          g_err = "gls_mesh_periodic_nodes: boundary ids must be two different ids in 0..31" + at;
+          return 1;
+        }
+      if (direction[p] < 0 || direction[p] >= dim)
+        {
+          g_err = "gls_mesh_periodic_nodes: direction out of range" + at;
+          return 1;
+        }
+      for (const int32_t id : {id_a[p], id_b[p]})
+        if ((m->nonplanar_bids >> id) & 1u)
+          {
+            g_err = "gls_mesh_periodic_nodes: boundary id " + std::to_string(id) +
+                    " has a curved or oblique face" + at;
+            return 1;
+          }
+      const int dir = direction[p];
+      // the coordinates that must agree; o[0] is the sort key
+      int o[2] = {0, 0}, no = 0;
+      for (int d = 0; d < dim; ++d)
+        if (d != dir)
+          o[no++] = d;
+      std::vector<int64_t> A, B;
+      for (int64_t i = 0; i < nn; ++i)
+        {
+          if ((m->node_bid[(size_t)i] >> id_a[p]) & 1u)
+            A.push_back(i);
+          if ((m->node_bid[(size_t)i] >> id_b[p]) & 1u)
+            B.push_back(i);
+        }
+      if (A.size() != B.size())
+        {
+          g_err = "gls_mesh_periodic_nodes: " + std::to_string(A.size()) + " nodes on id " +
+                  std::to_string(id_a[p]) + " but " + std::to_string(B.size()) + " on id " +
+                  std::to_string(id_b[p]) + at;
+          return 1;
+        }
+      auto key = [&](int64_t i) { return m->coords[(size_t)i * dim + o[0]]; };
+      std::sort(A.begin(), A.end(), [&](int64_t x, int64_t y) { return key(x) < key(y); });
+      std::vector<char> taken(A.size(), 0);
+      for (const int64_t b : B)
+        {
+          const double kb = key(b);
+          size_t       lo = std::lower_bound(A.begin(), A.end(), kb - tol,
+                                             [&](int64_t x, double v) { return key(x) < v; }) -
+                      A.begin();
+          int64_t found = -1;
+          for (size_t j = lo; j < A.size() && key(A[j]) <= kb + tol; ++j)
+            {
+              bool same = !taken[j];
+              for (int t = 1; t < no && same; ++t)
+                same = std::abs(m->coords[(size_t)A[j] * dim + o[t]] -
+                                m->coords[(size_t)b * dim + o[t]]) <= tol;
+              if (same)
+                {
+                  found    = A[j];
+                  taken[j] = 1;
+                  break;
+                }
+            }
+          if (found < 0)
+            {
+              g_err = "gls_mesh_periodic_nodes: node " + std::to_string(b) + " on id " +
+                      std::to_string(id_b[p]) + " has no partner on id " +
+                      std::to_string(id_a[p]) + at;
+              return 1;
+            }
+          if (found == b)
+            {
+              g_err = "gls_mesh_periodic_nodes: node " + std::to_string(b) +
+                      " lies on both ids of the pair" + at;
+              return 1;
+            }
+          // a node already eliminated by an earlier pair keeps its master; the
+          // chains are resolved below
+          if (node_master[b] == b)
+            node_master[b] = found;
+        }
+    }
+  // resolve chains (an edge node with two periodic directions): every node
+  // maps to a node that maps to itself
+  for (int64_t i = 0; i < nn; ++i)
+    {
+      int64_t r = i;
+      for (int hops = 0; node_master[r] != r; ++hops)
+        {
+          if (hops > 64)
+            {
+              g_err = "gls_mesh_periodic_nodes: the pairs form a cycle at node " +
+                      std::to_string(i);
+              return 1;
+            }
+          r = node_master[r];
+        }
+      node_master[i] = r;
+    }
+  return 0;
+}
+
+int
 gls_mesh_brick(const glsMesh *m, int *dims)
 {
   if (!m || !dims)

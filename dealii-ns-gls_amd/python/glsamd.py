@@ -78,7 +78,8 @@ class OpDesc(C.Structure):
                 ("cell_hmin", C.c_void_p), ("brick", C.c_int * 3),
                 ("n_outflow_faces", C.c_int64), ("outflow_cells", C.c_void_p),
                 ("outflow_face_no", C.c_void_p), ("outflow_kind", C.c_void_p),
-                ("mapping_degree", C.c_int), ("mapping_points", C.c_void_p)]
+                ("mapping_degree", C.c_int), ("mapping_points", C.c_void_p),
+                ("node_master", C.c_void_p)]
 
 OUTFLOW_KIND = {"cut": 1, "nitsche": 2}
 
@@ -535,7 +536,7 @@ class NavierStokesOperator:
     (MG levels, MGNumber=float, config.h:6-7)."""
 
     def __init__(self, mesh, cmask, precision="f64", cells=None, n_owned_nodes=None,
-                 brick=None, outflow=None, node_constraints=None):
+                 brick=None, outflow=None, node_constraints=None, node_master=None):
         import torch
         if not torch.cuda.is_available():
             raise GlsError("NavierStokesOperator needs a GPU (no CPU fallback by design)")
@@ -584,6 +585,18 @@ class NavierStokesOperator:
             pts = np.ascontiguousarray(pts if cells is None else pts[cells], dtype=np.float64)
             self._keep.append(pts)
             d.mapping_degree, d.mapping_points = int(mdeg), pts.ctypes.data
+        self.node_master = None
+        if node_master is not None:
+            # periodic boundaries (Mesh.periodic_nodes / Deck.node_master):
+            # node_master[slave] = master, every other node itself
+            if mapping is not None:
+                raise NotImplementedError("a periodic node map on an FE_Q_iso_Q1 level")
+            nm = np.ascontiguousarray(node_master, dtype=np.int64)
+            if nm.shape != (mesh.n_nodes,):
+                raise GlsError("node_master: expected one entry per node")
+            self._keep.append(nm)
+            self.node_master = nm
+            d.node_master = nm.ctypes.data
         h = C.c_void_p()
         _check(lib().gls_op_create(C.byref(d), C.byref(h)))
         self.h = h
@@ -1640,7 +1653,7 @@ class Multigrid:
 
 def build_gmg(meshes, cmasks, params, u_star_fine, history_fine=None, weights=None,
               precision="f32", coarse_iso_q1=False, outflow=None, node_constraints=None,
-              **mg_kwargs):
+              node_master=None, **mg_kwargs):
     """Level operators + transfers for a mesh hierarchy (coarse -> fine), the
     linearization point / history interpolated down level by level
     (interpolate_to_mg, main.cc:772-803, 815-832).  coarse_iso_q1: the
@@ -1648,8 +1661,10 @@ def build_gmg(meshes, cmasks, params, u_star_fine, history_fine=None, weights=No
     outflow: None, or (kind, boundary id): every level operator gets its
     mesh's outflow faces (the level operators take the outflow sets too,
     main.cc:520-527).  node_constraints: None, or per level (nodes, comp,
-    coef) or None (Deck.node_constraints of the level's mesh).  Returns
-    (mg, level_ops)."""
+    coef) or None (Deck.node_constraints of the level's mesh).  node_master:
+    None, or per level the periodic node map or None (Deck.node_master of the
+    level's mesh); the child lattices stay the meshes' own, gls_mg_create maps
+    them.  Returns (mg, level_ops)."""
     import torch
     if coarse_iso_q1:
         import glsmesh
@@ -1659,13 +1674,19 @@ def build_gmg(meshes, cmasks, params, u_star_fine, history_fine=None, weights=No
         node_constraints = [None] * len(meshes)
     if coarse_iso_q1 and node_constraints[0] is not None:
         raise GlsError("build_gmg: node constraints on an FE_Q_iso_Q1 level are not supported")
-    for m, cm, rows in zip(meshes, cmasks, node_constraints):
+    if node_master is None:
+        node_master = [None] * len(meshes)
+    if coarse_iso_q1 and any(nm is not None for nm in node_master):
+        raise NotImplementedError("build_gmg: a periodic node map with an FE_Q_iso_Q1 level is "
+                                  "not supported")
+    for m, cm, rows, nm in zip(meshes, cmasks, node_constraints, node_master):
         of = None
         if outflow is not None:
             import glsmesh
             fc, fn = glsmesh.boundary_faces(m, outflow[1])
             of = (fc, fn, outflow[0])
-        op = NavierStokesOperator(m, cm, precision, outflow=of, node_constraints=rows)
+        op = NavierStokesOperator(m, cm, precision, outflow=of, node_constraints=rows,
+                                  node_master=nm)
         op.set_parameters(**params)
         ops.append(op)
     child = [meshes[l - 1].child_lattice(meshes[l]) for l in range(1, len(meshes))]

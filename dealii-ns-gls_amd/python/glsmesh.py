@@ -49,6 +49,7 @@ def lib():
                                               vp, vp, vp, vp]
         L.gls_mesh_nonplanar_ids.argtypes = [vp]
         L.gls_mesh_nonplanar_ids.restype = C.c_uint32
+        L.gls_mesh_periodic_nodes.argtypes = [vp, C.c_int, vp, vp, vp, vp]
         L.gls_mesh_child_lattice.argtypes = [vp, vp, vp]
         L.gls_mesh_cell_measure.argtypes = [vp, vp, vp]
         L.gls_mesh_brick.argtypes = [vp, vp]
@@ -135,6 +136,20 @@ class Mesh:
                                              nodes.ctypes.data, comp.ctypes.data,
                                              coef.ctypes.data, normals.ctypes.data))
         return nodes, comp, coef, normals
+
+    def periodic_nodes(self, pairs):
+        """node_master [n_nodes] (int64) of the periodic boundary pairs
+        [(id_a, id_b, direction), ...] (gls_mesh_periodic_nodes): the nodes on
+        id_b are eliminated, node_master[slave] = master, every other node
+        maps to itself; chains are resolved."""
+        pairs = [tuple(int(v) for v in p) for p in pairs]
+        a = np.array([p[0] for p in pairs], dtype=np.int32)
+        b = np.array([p[1] for p in pairs], dtype=np.int32)
+        d = np.array([p[2] for p in pairs], dtype=np.int32)
+        out = np.zeros(self.n_nodes, dtype=np.int64)
+        _check(lib().gls_mesh_periodic_nodes(self._h, len(pairs), a.ctypes.data, b.ctypes.data,
+                                             d.ctypes.data, out.ctypes.data))
+        return out
 
     def brick(self):
         """(bx, by, bz): cells per brick (gls_mesh_brick)."""
@@ -333,6 +348,7 @@ class Deck:
     nonlinear_solver: str = "Newton"
     no_slip_cylinder: bool = True
     no_slip_wall: bool = True
+    wall_bc_periodic: bool = False  # "simulation use wall bc periodic"
     cylinder_shift: float = 0.005
     u_max: float = 1.0
     t_init: float = 0.0
@@ -474,7 +490,8 @@ class Deck:
         vel = [0]  # inflow: inhomogeneous DBC, zero in constraints_homogeneous
         slip = []
         walls = list(range(3, 3 + 2 * self.dim))
-        (vel if self.no_slip_wall else slip).extend(walls)
+        if not self.wall_bc_periodic:  # periodic walls carry no constraint of their own
+            (vel if self.no_slip_wall else slip).extend(walls)
         (vel if self.no_slip_cylinder else slip).append(2)
         p = []
         if self.outflow is None:
@@ -483,15 +500,38 @@ class Deck:
             vel.append(1)  # inhomogeneous DBC with the inflow function
         return vel, p, slip
 
+    def periodic_bcs(self):
+        """[(id_a, id_b, direction)] of "simulation use wall bc periodic"
+        (simulation.cc:406-412): the y-walls, and in 3D the z-walls."""
+        if not self.wall_bc_periodic or self.simulation != "cylinder":
+            return []
+        return [(3, 4, 1)] + ([(5, 6, 2)] if self.dim == 3 else [])
+
+    def node_master(self, mesh):
+        """The node identification of periodic_bcs() on `mesh` (what the
+        operator takes as node_master), or None without periodic walls."""
+        pairs = self.periodic_bcs()
+        if not pairs:
+            return None
+        if hasattr(mesh, "mapping_points"):
+            raise NotImplementedError("periodic boundaries on an FE_Q_iso_Q1 level")
+        return mesh.periodic_nodes(pairs)
+
     def node_constraints(self, mesh):
         """(nodes, comp, coef) of the no-normal-flux rows on the curved slip
         ids (the cylinder with "simulation no slip cylinder": false,
         simulation.cc:425-428, main.cc:285-287): what the operator takes as
-        node_constraints beside mask(mesh).  Empty without such an id."""
+        node_constraints beside mask(mesh).  Empty without such an id.  Rows on
+        the slave nodes of periodic walls are dropped (the slave takes its
+        master's value)."""
         if hasattr(mesh, "mapping_points"):
             raise NotImplementedError("node constraints on an FE_Q_iso_Q1 level")
         vel, _, _, curved = self.split_descriptor(mesh)
         nodes, comp, coef, _ = mesh.node_constraints(curved, vel)
+        master = self.node_master(mesh)
+        if master is not None and len(nodes):
+            keep = master[nodes] == nodes
+            nodes, comp, coef = nodes[keep], comp[keep], coef[keep]
         return nodes, comp, coef
 
     def split_descriptor(self, mesh):
@@ -610,6 +650,7 @@ def read_deck(path):
     d.nonlinear_solver = raw.get("nonlinear solver", "linearized")
     d.no_slip_cylinder = bool(raw.get("simulation no slip cylinder", True))
     d.no_slip_wall = bool(raw.get("simulation no slip wall", True))
+    d.wall_bc_periodic = bool(raw.get("simulation use wall bc periodic", False))
     d.cylinder_shift = float(raw.get("simulation geometry cylinder shift", 0.005))
     d.u_max = float(raw.get("simulation u max", 1.0))
     d.t_init = float(raw.get("simulation t init", 0.0))

@@ -121,6 +121,24 @@ int gls_mesh_no_normal_flux(const glsMesh *m, uint32_t slip_ids,
  * takes gls_mesh_no_normal_flux, the others gls_mesh_constraint_mask. */
 uint32_t gls_mesh_nonplanar_ids(const glsMesh *m);
 
+/* Periodic boundaries (DoFTools::make_periodicity_constraints on pairs of
+ * boundary ids, main.cc:289-291 / :495-497; "simulation use wall bc periodic"
+ * pairs ids 3/4 in direction 1 and, in 3D, 5/6 in direction 2): for each of
+ * the n_pairs pairs every node on id_b is matched to the node on id_a with
+ * equal coordinates in all but `direction` (tolerance 1e-9 x the mesh extent)
+ * and eliminated: node_master[node on id_b] = its partner.  Chains are
+ * resolved (a 3D edge node with two periodic directions has three slaves of
+ * one master), so node_master[node_master[i]] == node_master[i]; a free node
+ * maps to itself.  node_master has n_nodes entries: what glsOpDesc.node_master
+ * takes.  The id_b side is eliminated by convention; which side deal.II
+ * eliminates is not observable in the action on distributed vectors, and a
+ * binding passes deal.II's own map, so parity is unpinned.  Errors: a node
+ * without partner, unequal node counts on the two ids, an id with a curved or
+ * oblique face, direction out of range.  Returns 0 on success. */
+int gls_mesh_periodic_nodes(const glsMesh *m, int n_pairs, const int32_t *id_a,
+                            const int32_t *id_b, const int32_t *direction,
+                            int64_t *node_master);
+
 /* Cells are ordered brick-major inside every coarse cell: bricks of
  * dims[0] x dims[1] x dims[2] cells (min(2^n_ref, 4) per direction in 3D,
  * min(2^n_ref, 8) in 2D), lexicographic inside a brick, so the cell list is

@@ -155,6 +155,32 @@ typedef struct
    * outflow faces with it).                                                 */
   int             mapping_degree;  /* m, 1..3                                */
   const double   *mapping_points;  /* host [n_cells][(m+1)^dim][dim] or NULL */
+  /* periodic boundaries (DoFTools::make_periodicity_constraints, main.cc:
+   * 289-291, 495-497): host [n_nodes], node_master[slave] = the node whose
+   * unknowns the slave's are (all dim+1 components), node_master[i] = i for
+   * every other node; idempotent (what gls_mesh_periodic_nodes returns; a
+   * deal.II binding takes the constraint lines with a single entry of weight 1
+   * and no inhomogeneity).  NULL (zero-initialised descriptor): none.
+   * cell_nodes and node_coords stay the caller's (geometric) connectivity:
+   * geometry, brick discovery, face geometry and point location read it;
+   * every read or write of a vector or matrix entry goes through
+   * node_master[cell_nodes].  A slave is then in no cell and becomes a fully
+   * constrained row (identity in vmult, zero in the residuals, 1 in the
+   * diagonals, a unit row and column in the matrix).  The cell loop, the
+   * producers, the faces, surface_force, probe and get_max_u never read a
+   * slave's vector entries; vmult's identity row does: dst[slave] =
+   * src[slave], as on a Dirichlet dof, so a caller keeps the slave entries of
+   * its Krylov vectors finite (zero, or distributed).  The master takes the OR
+   * of its group's node_cmask bits.
+   * With C the map "slave := master" vmult computes C^T A C with identity rows
+   * on the slaves; gls_op_distribute also sets slave := master.  Errors: an
+   * entry out of range or not idempotent, a partitioned operator,
+   * mapping_points (an FE_Q_iso_Q1 level), a cell that
+   * lists one unknown twice (a period of one cell; the message names it).
+   * gls_op_vmult_cells works through the mapped connectivity.  Refused on
+   * such an operator: gls_dist_create, a node-constraint row on a slave node,
+   * the "nd" direct coarse solver of a multigrid whose coarse level has one. */
+  const int64_t  *node_master;
 } glsOpDesc;
 
 enum glsOutflow

@@ -95,6 +95,9 @@ class Operator
 {
 public:
   Operator() = default;
+  // (periodic boundaries: glsOpDesc::node_master, the map of
+  // DoFTools::make_periodicity_constraints' lines u_i = u_j; distribute()
+  // then also sets slave := master)
   explicit Operator(const glsOpDesc &desc) { check(gls_op_create(&desc, &h), "gls_op_create"); }
   ~Operator()
   {
