@@ -36,6 +36,16 @@ k_residual(T *__restrict__ t, const T *__restrict__ b, int64_t n)
     t[i] = b[i] - t[i];
 }
 
+// dst = src converted (the FP64 outer vectors of FP32 multigrid levels)
+template <typename Tin, typename Tout>
+__global__ void
+k_convert(Tout *__restrict__ dst, const Tin *__restrict__ src, int64_t n)
+{
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n)
+    dst[i] = (Tout)src[i];
+}
+
 inline void
 check_blas(rocblas_status st, const char *what)
 {

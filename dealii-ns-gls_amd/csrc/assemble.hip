@@ -270,16 +270,12 @@ launch_gather(const glsOp_ *op, const SystemMatrix *M, const void *E, int64_t c0
 {
   const int64_t np = M->plan.n_pairs;
   const dim3    g((unsigned)((np + 255) / 256));
-#define GLS_GATHER(NC)                                                                          \
-  hipLaunchKernelGGL((k_assemble_gather<T, NC>), g, dim3(256), 0, s, M->d_row_ptr,              \
-                     M->d_pair_row, M->d_pair_node, M->d_pair_off, M->d_inc_ptr, M->d_inc_cell, \
-                     M->d_inc_point, op->d_node_cmask, (const T *)E, c0, c1, (int)ndof_of(op),  \
-                     M->d_vals, np)
-  if (op->dim == 2)
-    GLS_GATHER(3);
-  else
-    GLS_GATHER(4);
-#undef GLS_GATHER
+  gls::with_int<3, 4>(op->dim + 1, "system matrix", [&](auto nc) {
+    hipLaunchKernelGGL((k_assemble_gather<T, decltype(nc)::value>), g, dim3(256), 0, s,
+                       M->d_row_ptr, M->d_pair_row, M->d_pair_node, M->d_pair_off, M->d_inc_ptr,
+                       M->d_inc_cell, M->d_inc_point, op->d_node_cmask, (const T *)E, c0, c1,
+                       (int)ndof_of(op), M->d_vals, np);
+  });
   HIP_THROW(hipGetLastError());
 }
 
@@ -288,18 +284,11 @@ void
 launch_vmult(const SystemMatrix *M, void *dst, const void *src, hipStream_t s)
 {
   const int64_t n = M->plan.n_dofs;
-#define GLS_VMULT(G)                                                                           \
-  hipLaunchKernelGGL((k_csr_vmult<T, G>), dim3((unsigned)((n * G + 255) / 256)), dim3(256), 0, \
-                     s, M->d_row_ptr, M->d_cols, M->d_vals, (const T *)src, (T *)dst, n)
-  if (M->group == 8)
-    GLS_VMULT(8);
-  else if (M->group == 16)
-    GLS_VMULT(16);
-  else if (M->group == 32)
-    GLS_VMULT(32);
-  else
-    GLS_VMULT(64);
-#undef GLS_VMULT
+  gls::with_int<8, 16, 32, 64>(M->group, "matrix-based vmult", [&](auto grp) {
+    constexpr int G = decltype(grp)::value;
+    hipLaunchKernelGGL((k_csr_vmult<T, G>), dim3((unsigned)((n * G + 255) / 256)), dim3(256), 0,
+                       s, M->d_row_ptr, M->d_cols, M->d_vals, (const T *)src, (T *)dst, n);
+  });
   HIP_THROW(hipGetLastError());
 }
 } // namespace
@@ -350,10 +339,7 @@ op_system_matrix_device(glsOp_ *op, hipStream_t s)
             op_element_matrices_device(op, E, b, e, s);
           }
           Section sc("ns::initialize_system_matrix::gather", s);
-          if (op->prec == GLS_F64)
-            launch_gather<double>(op, M, E, b, e, s);
-          else
-            launch_gather<float>(op, M, E, b, e, s);
+          with_real(op->prec, [&](auto t) { launch_gather<decltype(t)>(op, M, E, b, e, s); });
         }
       // node constraints: C^T A C on the same pattern
       nc_csr_device(op, M->d_row_ptr, M->d_cols, M->d_vals, s);
@@ -372,10 +358,7 @@ void
 op_csr_vmult_device(glsOp_ *op, void *dst, const void *src, hipStream_t s)
 {
   const SystemMatrix *M = op_system_matrix_device(op, s);
-  if (op->prec == GLS_F64)
-    launch_vmult<double>(M, dst, src, s);
-  else
-    launch_vmult<float>(M, dst, src, s);
+  with_real(op->prec, [&](auto t) { launch_vmult<decltype(t)>(M, dst, src, s); });
 }
 } // namespace gls
 

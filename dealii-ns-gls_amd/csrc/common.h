@@ -3,6 +3,9 @@
 
 #include <hip/hip_runtime.h>
 
+#include "dispatch.h"
+
+#include <algorithm>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -55,6 +58,21 @@ struct DeviceScope
   DeviceScope(const DeviceScope &)            = delete;
   DeviceScope &operator=(const DeviceScope &) = delete;
 };
+
+// host values converted to the precision `prec` (GLS_F64 / GLS_F32) and copied
+// to the device buffer *d, which is allocated first unless alloc is false
+inline void
+upload_real(int prec, void **d, const std::vector<double> &h, bool alloc = true)
+{
+  with_real(prec, [&](auto t) {
+    using T = decltype(t);
+    const std::vector<T> v(h.begin(), h.end());
+    if (alloc)
+      HIP_THROW(hipMalloc(d, std::max<size_t>(1, v.size() * sizeof(T))));
+    if (!v.empty())
+      HIP_THROW(hipMemcpy(*d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+  });
+}
 
 // what a brick launch runs: the brick kernel, and the shared-node reduction
 // of the owned rows, of the ghost rows (a partitioned operator's export

@@ -278,60 +278,42 @@ find_peer(const glsDist_ *d, int rank)
   return nullptr;
 }
 
-template <typename T>
+// rows of nc = dim + 1 components
 void
-launch_pack(glsDist_ *d, const void *src, hipStream_t s)
+pack(glsDist_ *d, const void *src, hipStream_t s)
 {
   const int nc = d->op->dim + 1;
   if (d->n_send == 0)
     return;
   const dim3 g((unsigned)((d->n_send * nc + 255) / 256));
-  if (nc == 4)
-    hipLaunchKernelGGL((gls::k_pack<T, 4>), g, dim3(256), 0, s, (T *)d->d_send_buf,
-                       (const T *)src, d->d_send_nodes, d->n_send);
-  else
-    hipLaunchKernelGGL((gls::k_pack<T, 3>), g, dim3(256), 0, s, (T *)d->d_send_buf,
-                       (const T *)src, d->d_send_nodes, d->n_send);
+  gls::with_real(d->op->prec, [&](auto t) {
+    using T = decltype(t);
+    gls::with_int<3, 4>(nc, "ghost pack", [&](auto c) {
+      hipLaunchKernelGGL((gls::k_pack<T, decltype(c)::value>), g, dim3(256), 0, s,
+                         (T *)d->d_send_buf, (const T *)src, d->d_send_nodes, d->n_send);
+    });
+  });
   HIP_THROW(hipGetLastError());
-}
-
-template <typename T>
-void
-launch_unpack(glsDist_ *d, void *dst, hipStream_t s, const gls::RelaxStep *rx)
-{
-  const T *rd    = rx ? (const T *)rx->d : nullptr;
-  const T  scale = rx ? (T)rx->omega : T(0);
-  const int nc = d->op->dim + 1;
-  if (d->n_un == 0)
-    return;
-  const dim3 g((unsigned)((d->n_un * nc + 255) / 256));
-  if (nc == 4)
-    hipLaunchKernelGGL((gls::k_unpack_add<T, 4>), g, dim3(256), 0, s, (T *)dst,
-                       (const T *)d->d_xrecv_buf, d->d_un_nodes, d->d_un_off, d->d_un_entry,
-                       d->n_un, rd, scale);
-  else
-    hipLaunchKernelGGL((gls::k_unpack_add<T, 3>), g, dim3(256), 0, s, (T *)dst,
-                       (const T *)d->d_xrecv_buf, d->d_un_nodes, d->d_un_off, d->d_un_entry,
-                       d->n_un, rd, scale);
-  HIP_THROW(hipGetLastError());
-}
-
-void
-pack(glsDist_ *d, const void *src, hipStream_t s)
-{
-  if (d->op->prec == GLS_F64)
-    launch_pack<double>(d, src, s);
-  else
-    launch_pack<float>(d, src, s);
 }
 
 void
 unpack(glsDist_ *d, void *dst, hipStream_t s, const gls::RelaxStep *rx = nullptr)
 {
-  if (d->op->prec == GLS_F64)
-    launch_unpack<double>(d, dst, s, rx);
-  else
-    launch_unpack<float>(d, dst, s, rx);
+  const int nc = d->op->dim + 1;
+  if (d->n_un == 0)
+    return;
+  const dim3 g((unsigned)((d->n_un * nc + 255) / 256));
+  gls::with_real(d->op->prec, [&](auto t) {
+    using T        = decltype(t);
+    const T *rd    = rx ? (const T *)rx->d : nullptr;
+    const T  scale = rx ? (T)rx->omega : T(0);
+    gls::with_int<3, 4>(nc, "ghost unpack", [&](auto c) {
+      hipLaunchKernelGGL((gls::k_unpack_add<T, decltype(c)::value>), g, dim3(256), 0, s, (T *)dst,
+                         (const T *)d->d_xrecv_buf, d->d_un_nodes, d->d_un_off, d->d_un_entry,
+                         d->n_un, rd, scale);
+    });
+  });
+  HIP_THROW(hipGetLastError());
 }
 
 ncclDataType_t

@@ -153,15 +153,6 @@ k_mul(T *y, const T *d, int64_t n)
     y[i] *= d[i];
 }
 
-template <typename Tin, typename Tout>
-__global__ void
-k_cvt(Tout *y, const Tin *x, int64_t n)
-{
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n)
-    y[i] = (Tout)x[i];
-}
-
 // g[l2g[node] nc + c] = v[node nc + c] over the owned nodes (g zeroed)
 template <typename T>
 __global__ void
@@ -251,12 +242,11 @@ team_dot(Team &t, int l, const std::vector<void *> &a, const std::vector<void *>
       glsDistMG_   *x  = t.m[r];
       const int64_t n  = x->n_owned[(size_t)l];
       const int     nb = (int)std::min<int64_t>(1024, std::max<int64_t>(1, (n + 255) / 256));
-      if (x->prec == GLS_F64)
-        hipLaunchKernelGGL(k_dot_part<double>, dim3(nb), dim3(256), 0, s, (const double *)a[r],
-                           (const double *)b[r], n, x->red);
-      else
-        hipLaunchKernelGGL(k_dot_part<float>, dim3(nb), dim3(256), 0, s, (const float *)a[r],
-                           (const float *)b[r], n, x->red);
+      gls::with_real(x->prec, [&](auto p) {
+        using T = decltype(p);
+        hipLaunchKernelGGL(k_dot_part<T>, dim3(nb), dim3(256), 0, s, (const T *)a[r],
+                           (const T *)b[r], n, x->red);
+      });
       hipLaunchKernelGGL(k_sum_part, dim3(1), dim3(256), 0, s, (const double *)x->red, nb,
                          x->red + RED - 1);
       res.push_back(x->red + RED - 1);
@@ -275,10 +265,10 @@ team_scale(Team &t, int l, const std::vector<void *> &x, double a, hipStream_t s
   for (int r = 0; r < t.n(); ++r)
     {
       const int64_t n = t.m[r]->n_dofs[(size_t)l];
-      if (t.m[r]->prec == GLS_F64)
-        hipLaunchKernelGGL(k_scale<double>, g1(n), dim3(256), 0, s, (double *)x[r], a, n);
-      else
-        hipLaunchKernelGGL(k_scale<float>, g1(n), dim3(256), 0, s, (float *)x[r], a, n);
+      gls::with_real(t.m[r]->prec, [&](auto p) {
+        using T = decltype(p);
+        hipLaunchKernelGGL(k_scale<T>, g1(n), dim3(256), 0, s, (T *)x[r], a, n);
+      });
     }
   HIP_THROW(hipGetLastError());
 }
@@ -343,6 +333,31 @@ copy_vec(void *dst, const void *src, size_t bytes, hipStream_t s)
   HIP_THROW(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s));
 }
 
+// the member's owned rows of the level-0 vector v into its zeroed global
+// FP64 buffer g_buf
+void
+scatter_owned(glsDistMG_ *x, const void *v, hipStream_t s)
+{
+  HIP_THROW(hipMemsetAsync(x->g_buf, 0, (size_t)x->ng0 * sizeof(double), s));
+  const int64_t nn = owned_nodes0(x);
+  gls::with_real(x->prec, [&](auto p) {
+    using T = decltype(p);
+    hipLaunchKernelGGL(k_scatter_owned<T>, g1(nn * x->nc), dim3(256), 0, s, x->g_buf,
+                       (const T *)v, x->d_l2g, nn, x->nc);
+  });
+}
+
+// g_buf (FP64) into dst in the redundant coarse operator's precision
+void
+global_to_coarse(glsDistMG_ *x, void *dst, hipStream_t s)
+{
+  if (x->coarse_op->prec == GLS_F64)
+    copy_vec(dst, x->g_buf, (size_t)x->ng0 * 8, s);
+  else
+    hipLaunchKernelGGL((k_convert<double, float>), g1(x->ng0), dim3(256), 0, s, (float *)dst,
+                       (const double *)x->g_buf, x->ng0);
+}
+
 // the coarse solve on level 0 (multigrid.cc:465-489): X[0] from B[0]
 void
 coarse(Team &t, hipStream_t s)
@@ -368,34 +383,21 @@ coarse(Team &t, hipStream_t s)
   std::vector<double *> g;
   for (auto *x : t.m)
     {
-      HIP_THROW(hipMemsetAsync(x->g_buf, 0, (size_t)x->ng0 * sizeof(double), s));
-      const int64_t nn = owned_nodes0(x);
-      if (x->prec == GLS_F64)
-        hipLaunchKernelGGL(k_scatter_owned<double>, g1(nn * x->nc), dim3(256), 0, s, x->g_buf,
-                           (const double *)x->B[0], x->d_l2g, nn, x->nc);
-      else
-        hipLaunchKernelGGL(k_scatter_owned<float>, g1(nn * x->nc), dim3(256), 0, s, x->g_buf,
-                           (const float *)x->B[0], x->d_l2g, nn, x->nc);
+      scatter_owned(x, x->B[0], s);
       g.push_back(x->g_buf);
     }
   HIP_THROW(hipGetLastError());
   gls::team_allreduce_sum(t.level(0), g.data(), m0->ng0, t.n(), s);
   for (auto *x : t.m)
     {
-      const int cp = gls_op_precision(x->coarse_op);
-      if (cp == GLS_F64)
-        copy_vec(x->g_rhs, x->g_buf, (size_t)x->ng0 * 8, s);
-      else
-        hipLaunchKernelGGL((k_cvt<double, float>), g1(x->ng0), dim3(256), 0, s,
-                           (float *)x->g_rhs, (const double *)x->g_buf, x->ng0);
+      global_to_coarse(x, x->g_rhs, s);
       check(gls_mg_vcycle(x->coarse_mg, x->g_sol, x->g_rhs, s));
       const int64_t nn = gls::dist_op(x->lv[0])->n_nodes;
-      if (x->prec == GLS_F64)
-        hipLaunchKernelGGL(k_gather_local<double>, g1(nn * x->nc), dim3(256), 0, s,
-                           (double *)x->X[0], (const double *)x->g_sol, x->d_l2g, nn, x->nc);
-      else
-        hipLaunchKernelGGL(k_gather_local<float>, g1(nn * x->nc), dim3(256), 0, s,
-                           (float *)x->X[0], (const float *)x->g_sol, x->d_l2g, nn, x->nc);
+      gls::with_real(x->prec, [&](auto p) {
+        using T = decltype(p);
+        hipLaunchKernelGGL(k_gather_local<T>, g1(nn * x->nc), dim3(256), 0, s, (T *)x->X[0],
+                           (const T *)x->g_sol, x->d_l2g, nn, x->nc);
+      });
     }
   HIP_THROW(hipGetLastError());
 }
@@ -429,14 +431,12 @@ v_step(Team &t, int l, hipStream_t s)
   for (auto *x : t.m)
     {
       const int64_t n = x->n_dofs[(size_t)l];
-      if (alone)
-        ; // T already holds b - A x
-      else if (x->prec == GLS_F64)
-        hipLaunchKernelGGL(k_residual<double>, g1(n), dim3(256), 0, s, (double *)x->T[l],
-                           (const double *)x->B[l], n);
-      else
-        hipLaunchKernelGGL(k_residual<float>, g1(n), dim3(256), 0, s, (float *)x->T[l],
-                           (const float *)x->B[l], n);
+      if (!alone) // (else T already holds b - A x)
+        gls::with_real(x->prec, [&](auto p) {
+          using T = decltype(p);
+          hipLaunchKernelGGL(k_residual<T>, g1(n), dim3(256), 0, s, (T *)x->T[l],
+                             (const T *)x->B[l], n);
+        });
       HIP_THROW(hipMemsetAsync(x->B[l - 1], 0, (size_t)x->n_dofs[(size_t)l - 1] * x->ts(), s));
       check(gls_mg_restrict_add(x->tr, l, x->B[l - 1], x->T[l], s));
     }
@@ -460,12 +460,10 @@ v_step(Team &t, int l, hipStream_t s)
 double
 power_iteration(Team &t, int l, hipStream_t s)
 {
-  const size_t b = (size_t)t.m[0]->n_dofs[(size_t)l] * t.m[0]->ts();
-  auto         X = per(t, [&](glsDistMG_ *x) { return x->X[l]; });
-  auto         Y = per(t, [&](glsDistMG_ *x) { return x->T[l]; });
+  auto X = per(t, [&](glsDistMG_ *x) { return x->X[l]; });
+  auto Y = per(t, [&](glsDistMG_ *x) { return x->T[l]; });
   for (auto *x : t.m)
     copy_vec(x->X[l], x->start[l], (size_t)x->n_dofs[(size_t)l] * x->ts(), s);
-  (void)b;
   const double nx = std::sqrt(team_dot(t, l, X, X, s));
   team_scale(t, l, X, nx > 0 ? 1.0 / nx : 0.0, s);
   double lam = 0;
@@ -475,12 +473,11 @@ power_iteration(Team &t, int l, hipStream_t s)
       for (auto *x : t.m)
         {
           const int64_t n = x->n_dofs[(size_t)l];
-          if (x->prec == GLS_F64)
-            hipLaunchKernelGGL(k_mul<double>, g1(n), dim3(256), 0, s, (double *)x->T[l],
-                               (const double *)x->invd[l], n);
-          else
-            hipLaunchKernelGGL(k_mul<float>, g1(n), dim3(256), 0, s, (float *)x->T[l],
-                               (const float *)x->invd[l], n);
+          gls::with_real(x->prec, [&](auto p) {
+            using T = decltype(p);
+            hipLaunchKernelGGL(k_mul<T>, g1(n), dim3(256), 0, s, (T *)x->T[l],
+                               (const T *)x->invd[l], n);
+          });
         }
       HIP_THROW(hipGetLastError());
       lam             = team_dot(t, l, X, Y, s);
@@ -559,13 +556,7 @@ gls_dist_mg_create(const glsDistMGDesc *d, const glsDist *levels, glsDistMG *out
               }
           void *sv = nullptr;
           HIP_THROW(hipMalloc(&sv, b));
-          if (m->prec == GLS_F64)
-            HIP_THROW(hipMemcpy(sv, x.data(), x.size() * 8, hipMemcpyHostToDevice));
-          else
-            {
-              std::vector<float> xf(x.begin(), x.end());
-              HIP_THROW(hipMemcpy(sv, xf.data(), xf.size() * 4, hipMemcpyHostToDevice));
-            }
+          gls::upload_real(m->prec, &sv, x, false);
           m->start.push_back(sv);
         }
       m->omega.assign(nl, 1.0);
@@ -742,30 +733,13 @@ gls_dist_mg_set_linearization_point(glsDistMG const *team, int n, const void *co
               for (int r = 0; r < n; ++r)
                 {
                   glsDistMG_ *x = t.m[r];
-                  HIP_THROW(hipMemsetAsync(x->g_buf, 0, (size_t)x->ng0 * 8, s));
-                  const int64_t nn = owned_nodes0(x);
-                  if (x->prec == GLS_F64)
-                    hipLaunchKernelGGL(k_scatter_owned<double>, g1(nn * x->nc), dim3(256), 0, s,
-                                       x->g_buf, (const double *)buf(r, 0, v), x->d_l2g, nn,
-                                       x->nc);
-                  else
-                    hipLaunchKernelGGL(k_scatter_owned<float>, g1(nn * x->nc), dim3(256), 0, s,
-                                       x->g_buf, (const float *)buf(r, 0, v), x->d_l2g, nn,
-                                       x->nc);
+                  scatter_owned(x, buf(r, 0, v), s);
                   g.push_back(x->g_buf);
                 }
               HIP_THROW(hipGetLastError());
               gls::team_allreduce_sum(t.level(0), g.data(), t.m[0]->ng0, n, s);
               for (int r = 0; r < n; ++r)
-                {
-                  glsDistMG_ *x = t.m[r];
-                  if (x->coarse_op->prec == GLS_F64)
-                    copy_vec(gv[(size_t)r][(size_t)v], x->g_buf, (size_t)x->ng0 * 8, s);
-                  else
-                    hipLaunchKernelGGL((k_cvt<double, float>), g1(x->ng0), dim3(256), 0, s,
-                                       (float *)gv[(size_t)r][(size_t)v],
-                                       (const double *)x->g_buf, x->ng0);
-                }
+                global_to_coarse(t.m[r], gv[(size_t)r][(size_t)v], s);
             }
           HIP_THROW(hipGetLastError());
           for (int r = 0; r < n; ++r)
@@ -919,8 +893,8 @@ gls_dist_mg_vcycle(glsDistMG const *team, int n, void *const *dst, const void *c
       const int64_t nd  = x->n_dofs[(size_t)top];
       const bool    cvt = x->desc.outer_precision == GLS_F64 && x->prec == GLS_F32;
       if (cvt)
-        hipLaunchKernelGGL((k_cvt<double, float>), g1(nd), dim3(256), 0, s, (float *)x->B[top],
-                           (const double *)src[r], nd);
+        hipLaunchKernelGGL((k_convert<double, float>), g1(nd), dim3(256), 0, s,
+                           (float *)x->B[top], (const double *)src[r], nd);
       else
         copy_vec(x->B[top], src[r], (size_t)nd * x->ts(), s);
     }
@@ -932,8 +906,8 @@ gls_dist_mg_vcycle(glsDistMG const *team, int n, void *const *dst, const void *c
       const int64_t nd  = x->n_dofs[(size_t)top];
       const bool    cvt = x->desc.outer_precision == GLS_F64 && x->prec == GLS_F32;
       if (cvt)
-        hipLaunchKernelGGL((k_cvt<float, double>), g1(nd), dim3(256), 0, s, (double *)dst[r],
-                           (const float *)x->X[top], nd);
+        hipLaunchKernelGGL((k_convert<float, double>), g1(nd), dim3(256), 0, s,
+                           (double *)dst[r], (const float *)x->X[top], nd);
       else
         copy_vec(dst[r], x->X[top], (size_t)nd * x->ts(), s);
     }

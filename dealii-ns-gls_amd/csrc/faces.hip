@@ -285,15 +285,6 @@ invert_jacobian(int dim, const double *J, double *inv, double &det)
   inv[8] = (J[0] * J[4] - J[1] * J[3]) / det;
 }
 
-template <typename T>
-void
-upload_as(void **d, const std::vector<double> &h)
-{
-  std::vector<T> t(h.begin(), h.end());
-  HIP_THROW(hipMalloc(d, std::max<size_t>(1, t.size() * sizeof(T))));
-  if (!t.empty())
-    HIP_THROW(hipMemcpy(*d, t.data(), t.size() * sizeof(T), hipMemcpyHostToDevice));
-}
 } // namespace
 
 void
@@ -418,26 +409,13 @@ faces_setup(glsOp_ *op, const glsOpDesc *d)
   HIP_THROW(hipMalloc((void **)&F.d_kind, kind.size() * sizeof(int32_t)));
   HIP_THROW(hipMemcpy(F.d_kind, kind.data(), kind.size() * sizeof(int32_t), hipMemcpyHostToDevice));
   const std::vector<double> zero((size_t)F.n * nqf * dim, 0.0);
-  if (op->prec == GLS_F64)
-    {
-      upload_as<double>(&F.d_beta, beta);
-      upload_as<double>(&F.d_jxw, jxw);
-      upload_as<double>(&F.d_normal, nrm);
-      upload_as<double>(&F.d_phi, phi);
-      upload_as<double>(&F.d_dn, dnv);
-      upload_as<double>(&F.d_ustar, zero);
-      upload_as<double>(&F.d_target, zero);
-    }
-  else
-    {
-      upload_as<float>(&F.d_beta, beta);
-      upload_as<float>(&F.d_jxw, jxw);
-      upload_as<float>(&F.d_normal, nrm);
-      upload_as<float>(&F.d_phi, phi);
-      upload_as<float>(&F.d_dn, dnv);
-      upload_as<float>(&F.d_ustar, zero);
-      upload_as<float>(&F.d_target, zero);
-    }
+  upload_real(op->prec, &F.d_beta, beta);
+  upload_real(op->prec, &F.d_jxw, jxw);
+  upload_real(op->prec, &F.d_normal, nrm);
+  upload_real(op->prec, &F.d_phi, phi);
+  upload_real(op->prec, &F.d_dn, dnv);
+  upload_real(op->prec, &F.d_ustar, zero);
+  upload_real(op->prec, &F.d_target, zero);
 }
 
 void
@@ -460,12 +438,11 @@ faces_linearization(const glsOp_ *op, const void *lin, hipStream_t s)
     return;
   const int64_t m = F.n * F.nqf;
   const dim3    g((unsigned)((m + 127) / 128));
-  if (op->prec == GLS_F64)
-    hipLaunchKernelGGL(k_face_ustar<double>, g, dim3(128), 0, s, face_args<double>(op), F.n,
-                       (double *)F.d_ustar, (const double *)lin);
-  else
-    hipLaunchKernelGGL(k_face_ustar<float>, g, dim3(128), 0, s, face_args<float>(op), F.n,
-                       (float *)F.d_ustar, (const float *)lin);
+  with_real(op->prec, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_face_ustar<T>, g, dim3(128), 0, s, face_args<T>(op), F.n,
+                       (T *)F.d_ustar, (const T *)lin);
+  });
   HIP_THROW(hipGetLastError());
 }
 
@@ -476,24 +453,13 @@ faces_apply(const glsOp_ *op, bool residual, void *dst, const void *src, hipStre
   if (!F.n)
     return;
   const dim3 g((unsigned)F.n);
-  if (op->prec == GLS_F64)
-    {
-      if (residual)
-        hipLaunchKernelGGL((k_face_apply<double, true>), g, dim3(FACE_BLOCK), 0, s,
-                           face_args<double>(op), (double *)dst, (const double *)src);
-      else
-        hipLaunchKernelGGL((k_face_apply<double, false>), g, dim3(FACE_BLOCK), 0, s,
-                           face_args<double>(op), (double *)dst, (const double *)src);
-    }
-  else
-    {
-      if (residual)
-        hipLaunchKernelGGL((k_face_apply<float, true>), g, dim3(FACE_BLOCK), 0, s,
-                           face_args<float>(op), (float *)dst, (const float *)src);
-      else
-        hipLaunchKernelGGL((k_face_apply<float, false>), g, dim3(FACE_BLOCK), 0, s,
-                           face_args<float>(op), (float *)dst, (const float *)src);
-    }
+  with_real(op->prec, [&](auto t) {
+    using T = decltype(t);
+    with_int<0, 1>(residual, "outflow faces", [&](auto r) {
+      hipLaunchKernelGGL((k_face_apply<T, decltype(r)::value != 0>), g, dim3(FACE_BLOCK), 0, s,
+                         face_args<T>(op), (T *)dst, (const T *)src);
+    });
+  });
   HIP_THROW(hipGetLastError());
 }
 
@@ -504,15 +470,19 @@ faces_diagonal(const glsOp_ *op, void *diag, bool f64_out, hipStream_t s)
   if (!F.n)
     return;
   const dim3 g((unsigned)F.n);
-  if (op->prec == GLS_F64)
-    hipLaunchKernelGGL((k_face_diag<double, double>), g, dim3(FACE_BLOCK), 0, s,
-                       face_args<double>(op), (double *)diag);
-  else if (f64_out)
-    hipLaunchKernelGGL((k_face_diag<float, double>), g, dim3(FACE_BLOCK), 0, s,
-                       face_args<float>(op), (double *)diag);
-  else
-    hipLaunchKernelGGL((k_face_diag<float, float>), g, dim3(FACE_BLOCK), 0, s,
-                       face_args<float>(op), (float *)diag);
+  auto launch = [&](auto t, auto o) {
+    using T = decltype(t);
+    using O = decltype(o);
+    hipLaunchKernelGGL((k_face_diag<T, O>), g, dim3(FACE_BLOCK), 0, s, face_args<T>(op),
+                       (O *)diag);
+  };
+  // FP64 operators write FP64 only; FP32 ones FP64 or their own precision
+  with_real(op->prec, [&](auto t) {
+    if constexpr (std::is_same<decltype(t), float>::value)
+      if (!f64_out)
+        return launch(t, float{});
+    launch(t, double{});
+  });
   HIP_THROW(hipGetLastError());
 }
 
@@ -523,12 +493,11 @@ faces_element_matrices(const glsOp_ *op, void *emat, int64_t b, int64_t e, hipSt
   if (!F.n)
     return;
   const dim3 g((unsigned)F.n);
-  if (op->prec == GLS_F64)
-    hipLaunchKernelGGL(k_face_emat<double>, g, dim3(FACE_BLOCK), 0, s, face_args<double>(op),
-                       (double *)emat, b, e);
-  else
-    hipLaunchKernelGGL(k_face_emat<float>, g, dim3(FACE_BLOCK), 0, s, face_args<float>(op),
-                       (float *)emat, b, e);
+  with_real(op->prec, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_face_emat<T>, g, dim3(FACE_BLOCK), 0, s, face_args<T>(op), (T *)emat, b,
+                       e);
+  });
   HIP_THROW(hipGetLastError());
 }
 } // namespace gls
@@ -568,15 +537,12 @@ gls_op_set_outflow_target(glsOp op, const double *target, void *stream)
     return 0;
   // pageable host source: copied and waited for (a per-time-step update)
   hipStream_t s = (hipStream_t)stream;
-  if (op->prec == GLS_F64)
-    HIP_THROW(hipMemcpyAsync(F.d_target, target, m * sizeof(double), hipMemcpyHostToDevice, s));
-  else
-    {
-      std::vector<float> t(target, target + m);
-      HIP_THROW(hipMemcpyAsync(F.d_target, t.data(), m * sizeof(float), hipMemcpyHostToDevice, s));
-      HIP_THROW(hipStreamSynchronize(s));
-    }
-  HIP_THROW(hipStreamSynchronize(s));
+  gls::with_real(op->prec, [&](auto t) {
+    using T = decltype(t);
+    const std::vector<T> v(target, target + m);
+    HIP_THROW(hipMemcpyAsync(F.d_target, v.data(), m * sizeof(T), hipMemcpyHostToDevice, s));
+    HIP_THROW(hipStreamSynchronize(s));
+  });
   gls::op_invalidate_system(op);
   GLS_CATCH
 }

@@ -356,29 +356,6 @@ launch_probe(const glsOp_ *op, const void *vec, bool avg, hipStream_t s)
                      F.d_pxi, make_rule(1, k), F.n_points, avg ? 1 : 0, F.d_pval);
 }
 
-template <typename T>
-void
-dispatch(const glsOp_ *op, const void *vec, bool probe, bool avg, hipStream_t s)
-{
-#define GLS_CASE(D, K)                          \
-  if (op->dim == D && op->degree == K)          \
-    {                                           \
-      if (probe)                                \
-        launch_probe<D, K, T>(op, vec, avg, s); \
-      else                                      \
-        launch_force<D, K, T>(op, vec, s);      \
-      return;                                   \
-    }
-  GLS_CASE(2, 1)
-  GLS_CASE(2, 2)
-  GLS_CASE(2, 3)
-  GLS_CASE(3, 1)
-  GLS_CASE(3, 2)
-  GLS_CASE(3, 3)
-#undef GLS_CASE
-  throw std::runtime_error("forces: no instantiation for this (dim, degree)");
-}
-
 // caller cell -> internal cell
 std::vector<int64_t>
 internal_cells(const glsOp_ *op)
@@ -452,12 +429,11 @@ forces_run(const glsOp_ *op, const void *vec, hipStream_t s)
 {
   const Forces &F = op->forces;
   if (F.n_faces > 0)
-    {
-      if (op->prec == GLS_F64)
-        dispatch<double>(op, vec, false, false, s);
-      else
-        dispatch<float>(op, vec, false, false, s);
-    }
+    with_real(op->prec, [&](auto t) {
+      with_dim_degree(op->dim, op->degree, "forces", [&](auto d, auto k) {
+        launch_force<decltype(d)::value, decltype(k)::value, decltype(t)>(op, vec, s);
+      });
+    });
   hipLaunchKernelGGL(k_force_sum, dim3(1), dim3(256), 0, s, (const double *)F.d_out, F.n_faces,
                      op->dim, F.d_total);
   HIP_THROW(hipGetLastError());
@@ -474,10 +450,11 @@ probe_run(glsOp_ *op, const void *vec, bool avg, double *values, hipStream_t s)
   if (F.n_points == 0)
     return;
   const void *x = op->stage.in_vec(vec, 0, s);
-  if (op->prec == GLS_F64)
-    dispatch<double>(op, x, true, avg, s);
-  else
-    dispatch<float>(op, x, true, avg, s);
+  with_real(op->prec, [&](auto t) {
+    with_dim_degree(op->dim, op->degree, "probe", [&](auto d, auto k) {
+      launch_probe<decltype(d)::value, decltype(k)::value, decltype(t)>(op, x, avg, s);
+    });
+  });
   HIP_THROW(hipGetLastError());
   // the kernel wrote host-mapped memory: complete after the synchronize
   HIP_THROW(hipStreamSynchronize(s));

@@ -108,13 +108,6 @@ upload(void **dptr, const std::vector<T> &h)
     HIP_THROW(hipMemcpy(*dptr, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
 }
 
-template <typename T>
-std::vector<T>
-convert(const std::vector<double> &v)
-{
-  return std::vector<T>(v.begin(), v.end());
-}
-
 // host twin of gls::qindex (kernels.h): [plane][cell][line] position of q
 // point p of `cell`
 int64_t
@@ -769,10 +762,10 @@ struct Impl
     constexpr int CPB = (64 / nq > 0 ? 64 / nq : 1) * (BLOCK / 64);
     const int64_t nv  = (e - b) * (int64_t)nq * (dim + 1);
     const dim3    grid((unsigned)((nv + CPB - 1) / CPB));
-    if (mode == MODE_NEWTON)
-      hipLaunchKernelGGL((k_apply<dim, k, T, MODE_NEWTON, true>), grid, dim3(BLOCK), 0, s, a);
-    else
-      hipLaunchKernelGGL((k_apply<dim, k, T, MODE_FIXED, true>), grid, dim3(BLOCK), 0, s, a);
+    with_int<MODE_NEWTON, MODE_FIXED>(mode, "element matrices", [&](auto m) {
+      hipLaunchKernelGGL((k_apply<dim, k, T, decltype(m)::value, true>), grid, dim3(BLOCK), 0, s,
+                         a);
+    });
     HIP_THROW(hipGetLastError());
   }
 
@@ -790,21 +783,17 @@ struct Impl
     constexpr int CPB = (64 / nq > 0 ? 64 / nq : 1) * (BLOCK / 64);
     const int64_t nv  = (e - b) * (diag ? (int64_t)nq * (dim + 1) : 1);
     const dim3    grid((unsigned)((nv + CPB - 1) / CPB));
-#define GLS_LAUNCH(M, DG) hipLaunchKernelGGL((k_apply<dim, k, T, M, DG>), grid, dim3(BLOCK), 0, s, a)
+    // the diagonal / element-matrix form exists for the two vmult modes only
     if (diag)
-      {
-        if (mode == MODE_NEWTON)
-          GLS_LAUNCH(MODE_NEWTON, true);
-        else
-          GLS_LAUNCH(MODE_FIXED, true);
-      }
-    else if (mode == MODE_NEWTON)
-      GLS_LAUNCH(MODE_NEWTON, false);
-    else if (mode == MODE_FIXED)
-      GLS_LAUNCH(MODE_FIXED, false);
+      with_int<MODE_NEWTON, MODE_FIXED>(mode, "cell apply (diagonal)", [&](auto m) {
+        hipLaunchKernelGGL((k_apply<dim, k, T, decltype(m)::value, true>), grid, dim3(BLOCK), 0, s,
+                           a);
+      });
     else
-      GLS_LAUNCH(MODE_RESIDUAL, false);
-#undef GLS_LAUNCH
+      with_int<MODE_NEWTON, MODE_FIXED, MODE_RESIDUAL>(mode, "cell apply", [&](auto m) {
+        hipLaunchKernelGGL((k_apply<dim, k, T, decltype(m)::value, false>), grid, dim3(BLOCK), 0,
+                           s, a);
+      });
     HIP_THROW(hipGetLastError());
   }
 
@@ -817,30 +806,18 @@ struct Impl
     if constexpr (!DET)
       if (a.det) // the deterministic accumulation: its own instantiations
         return launch_brick<M, true>(n_units, lds, geo, s, a);
-    // two-layer bricks (3D Q2, build_bricks): two lattice chunks per thread
-    if constexpr (dim == 3 && k == 2)
-      if (a.L > BrickLattice<dim, k, 1>::L)
-        {
-          if (geo == GEO_GEN)
-            hipLaunchKernelGGL((k_brick<dim, k, T, M, GEO_GEN, 2, DET>), dim3((unsigned)n_units),
-                               dim3(BLOCK), lds, s, a);
-          else if (geo == GEO_CART)
-            hipLaunchKernelGGL((k_brick<dim, k, T, M, GEO_CART, 2, DET>), dim3((unsigned)n_units),
-                               dim3(BLOCK), lds, s, a);
-          else
-            hipLaunchKernelGGL((k_brick<dim, k, T, M, GEO_ANY, 2, DET>), dim3((unsigned)n_units),
-                               dim3(BLOCK), lds, s, a);
-          return;
-        }
-    if (geo == GEO_GEN)
-      hipLaunchKernelGGL((k_brick<dim, k, T, M, GEO_GEN, 1, DET>), dim3((unsigned)n_units),
-                         dim3(BLOCK), lds, s, a);
-    else if (geo == GEO_CART)
-      hipLaunchKernelGGL((k_brick<dim, k, T, M, GEO_CART, 1, DET>), dim3((unsigned)n_units),
-                         dim3(BLOCK), lds, s, a);
-    else
-      hipLaunchKernelGGL((k_brick<dim, k, T, M, GEO_ANY, 1, DET>), dim3((unsigned)n_units),
-                         dim3(BLOCK), lds, s, a);
+    auto launch = [&](auto g, auto z) {
+      hipLaunchKernelGGL((k_brick<dim, k, T, M, decltype(g)::value, decltype(z)::value, DET>),
+                         dim3((unsigned)n_units), dim3(BLOCK), lds, s, a);
+    };
+    with_int<GEO_GEN, GEO_CART, GEO_ANY>(geo, "brick kernel geometry", [&](auto g) {
+      // two-layer bricks (3D Q2 only, build_bricks): two lattice chunks per thread
+      if constexpr (dim == 3 && k == 2)
+        with_int<1, 2>(a.L > BrickLattice<dim, k, 1>::L ? 2 : 1, "brick kernel layers",
+                       [&](auto z) { launch(g, z); });
+      else
+        launch(g, std::integral_constant<int, 1>{});
+    });
   }
 
   // the brick kernels' arguments for one apply (dst, src; rx: the fused
@@ -992,12 +969,9 @@ struct Impl
           {
             const int    geo = brick_geo(op);
             const size_t lds = BrickLDS<dim, k, T>::bytes(a.LP);
-            if (mode == MODE_NEWTON)
-              launch_brick<MODE_NEWTON>(b1 - b0, lds, geo, s, a);
-            else if (mode == MODE_FIXED)
-              launch_brick<MODE_FIXED>(b1 - b0, lds, geo, s, a);
-            else
-              launch_brick<MODE_RESIDUAL>(b1 - b0, lds, geo, s, a);
+            with_int<MODE_NEWTON, MODE_FIXED, MODE_RESIDUAL>(mode, "brick kernel", [&](auto m) {
+              launch_brick<decltype(m)::value>(b1 - b0, lds, geo, s, a);
+            });
             HIP_THROW(hipGetLastError());
           }
         // the shared-node reduction over all shared nodes, or over the owned
@@ -1064,10 +1038,9 @@ struct Impl
       return;
     auto launch = [&](const DiagArgs<T, dim, n> &x, int64_t cells) {
       const dim3 grid((unsigned)((cells + CPB - 1) / CPB));
-      if (mode == MODE_NEWTON)
-        hipLaunchKernelGGL((k_diag<dim, k, T, MODE_NEWTON>), grid, dim3(BLOCK), 0, s, x);
-      else
-        hipLaunchKernelGGL((k_diag<dim, k, T, MODE_FIXED>), grid, dim3(BLOCK), 0, s, x);
+      with_int<MODE_NEWTON, MODE_FIXED>(mode, "diagonal", [&](auto m) {
+        hipLaunchKernelGGL((k_diag<dim, k, T, decltype(m)::value>), grid, dim3(BLOCK), 0, s, x);
+      });
       HIP_THROW(hipGetLastError());
     };
     if (!op_deterministic(op))
@@ -1119,103 +1092,25 @@ struct Impl
   }
 };
 
-using ApplyFn   = void (*)(const glsOp_ *, int, bool, void *, const void *, int64_t, int64_t,
-                         hipStream_t);
-using DiagFn    = void (*)(const glsOp_ *, int, double *, hipStream_t);
-
-template <typename T>
-DiagFn
-select_diag_t(int dim, int k)
+// f(Impl<dim, degree, T>{}) for the operator's (dim, degree) and precision
+template <typename F>
+auto
+with_impl(const glsOp_ *op, const char *who, F &&f) -> decltype(f(Impl<2, 1, double>{}))
 {
-#define GLS_CASE(D, K)     \
-  if (dim == D && k == K)  \
-    return &Impl<D, K, T>::diag;
-  GLS_CASE(2, 1)
-  GLS_CASE(2, 2)
-  GLS_CASE(2, 3)
-  GLS_CASE(3, 1)
-  GLS_CASE(3, 2)
-  GLS_CASE(3, 3)
-#undef GLS_CASE
-  return nullptr;
-}
-using ProduceFn = void (*)(const glsOp_ *, int, const void *, hipStream_t);
-using EmatFn    = void (*)(const glsOp_ *, int, void *, int64_t, int64_t, hipStream_t);
-
-template <typename T>
-EmatFn
-select_emat_t(int dim, int k)
-{
-#define GLS_CASE(D, K)     \
-  if (dim == D && k == K)  \
-    return &Impl<D, K, T>::element_matrices;
-  GLS_CASE(2, 1)
-  GLS_CASE(2, 2)
-  GLS_CASE(2, 3)
-  GLS_CASE(3, 1)
-  GLS_CASE(3, 2)
-  GLS_CASE(3, 3)
-#undef GLS_CASE
-  return nullptr;
+  return with_real(op->prec, [&](auto t) {
+    return with_dim_degree(op->dim, op->degree, who, [&](auto d, auto k) {
+      return f(Impl<decltype(d)::value, decltype(k)::value, decltype(t)>{});
+    });
+  });
 }
 
-template <typename T>
+// the table producer (what: 0 linearisation point, 1 time history, 2 old
+// gradients) of the operator's instantiation
 void
-select_t(int dim, int k, ApplyFn &af, ProduceFn &pf)
+produce(const glsOp_ *op, int what, const void *vec, hipStream_t s)
 {
-  af = nullptr;
-  pf = nullptr;
-#define GLS_CASE(D, K)                  \
-  if (dim == D && k == K)               \
-    {                                   \
-      af = &Impl<D, K, T>::apply;       \
-      pf = &Impl<D, K, T>::produce;     \
-    }
-  GLS_CASE(2, 1)
-  GLS_CASE(2, 2)
-  GLS_CASE(2, 3)
-  GLS_CASE(3, 1)
-  GLS_CASE(3, 2)
-  GLS_CASE(3, 3)
-#undef GLS_CASE
-}
-
-void
-select(const glsOp_ *op, ApplyFn &af, ProduceFn &pf)
-{
-  if (op->prec == GLS_F64)
-    select_t<double>(op->dim, op->degree, af, pf);
-  else
-    select_t<float>(op->dim, op->degree, af, pf);
-  if (!af)
-    throw std::runtime_error("no kernel instantiation for this (dim, degree)");
-}
-
-using BrickFn = void (*)(const glsOp_ *, int, void *, const void *, int64_t, int64_t, int,
-                         hipStream_t, const RelaxStep *);
-
-template <typename T>
-BrickFn
-select_brick_t(int dim, int k)
-{
-#define GLS_CASE(D, K)     \
-  if (dim == D && k == K)  \
-    return &Impl<D, K, T>::brick;
-  GLS_CASE(2, 1)
-  GLS_CASE(2, 2)
-  GLS_CASE(2, 3)
-  GLS_CASE(3, 1)
-  GLS_CASE(3, 2)
-  GLS_CASE(3, 3)
-#undef GLS_CASE
-  return nullptr;
-}
-
-BrickFn
-select_brick(const glsOp_ *op)
-{
-  return op->prec == GLS_F64 ? select_brick_t<double>(op->dim, op->degree) :
-                               select_brick_t<float>(op->dim, op->degree);
+  with_impl(op, "table producer",
+            [&](auto impl) { decltype(impl)::produce(op, what, vec, s); });
 }
 
 int
@@ -1230,22 +1125,17 @@ grid1d(int64_t n)
   return dim3((unsigned)((n + 255) / 256));
 }
 
-template <typename T>
-void
-launch_init(const glsOp_ *op, void *dst, const void *src, hipStream_t s)
-{
-  hipLaunchKernelGGL(k_init_dst<T>, grid1d(op->n_dofs), dim3(256), 0, s, (T *)dst,
-                     (const T *)src, op->d_cbits, op->n_owned_dofs, op->n_dofs);
-  HIP_THROW(hipGetLastError());
-}
-
+// dst = the identity rows of src on the constrained dofs, zero elsewhere (the
+// per-cell kernels add into it)
 void
 init_dst(const glsOp_ *op, void *dst, const void *src, hipStream_t s)
 {
-  if (op->prec == GLS_F64)
-    launch_init<double>(op, dst, src, s);
-  else
-    launch_init<float>(op, dst, src, s);
+  with_real(op->prec, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_init_dst<T>, grid1d(op->n_dofs), dim3(256), 0, s, (T *)dst,
+                       (const T *)src, op->d_cbits, op->n_owned_dofs, op->n_dofs);
+  });
+  HIP_THROW(hipGetLastError());
 }
 
 // the cell loop and the outflow faces: A x with the Dirichlet identity rows,
@@ -1253,17 +1143,17 @@ init_dst(const glsOp_ *op, void *dst, const void *src, hipStream_t s)
 void
 vmult_unwrapped(const glsOp_ *op, void *dst, const void *src, hipStream_t s)
 {
-  ApplyFn   af;
-  ProduceFn pf;
-  select(op, af, pf);
-  if (op->use_brick)
-    select_brick(op)(op, vmult_mode(op), dst, src, 0, op->n_bricks, BRICK_RUN | BRICK_REDUCE, s,
-                     nullptr);
-  else
-    {
-      init_dst(op, dst, src, s);
-      af(op, vmult_mode(op), false, dst, src, 0, op->n_cells, s);
-    }
+  with_impl(op, "vmult", [&](auto impl) {
+    using I = decltype(impl);
+    if (op->use_brick)
+      I::brick(op, vmult_mode(op), dst, src, 0, op->n_bricks, BRICK_RUN | BRICK_REDUCE, s,
+               nullptr);
+    else
+      {
+        init_dst(op, dst, src, s);
+        I::apply(op, vmult_mode(op), false, dst, src, 0, op->n_cells, s);
+      }
+  });
   gls::faces_apply(op, false, dst, src, s);
 }
 
@@ -1293,10 +1183,9 @@ void
 brick_launch(const glsOp_ *op, int mode, void *dst, const void *src, int64_t b0, int64_t b1,
              int what, hipStream_t s, const RelaxStep *rx)
 {
-  BrickFn f = select_brick(op);
-  if (!f)
-    throw std::runtime_error("no brick kernel for this (dim, degree)");
-  f(op, mode, dst, src, b0, b1, what, s, rx);
+  with_impl(op, "brick kernel", [&](auto impl) {
+    decltype(impl)::brick(op, mode, dst, src, b0, b1, what, s, rx);
+  });
 }
 
 int
@@ -1424,24 +1313,11 @@ permute(bool in_dir, size_t ts, void *out, const void *in, const int64_t *map, i
         hipStream_t s)
 {
   const dim3 g((unsigned)((n + 255) / 256));
-  if (ts == 8)
-    {
-      if (in_dir)
-        hipLaunchKernelGGL(k_permute_in<double>, g, dim3(256), 0, s, (double *)out,
-                           (const double *)in, map, n);
-      else
-        hipLaunchKernelGGL(k_permute_out<double>, g, dim3(256), 0, s, (double *)out,
-                           (const double *)in, map, n);
-    }
-  else
-    {
-      if (in_dir)
-        hipLaunchKernelGGL(k_permute_in<float>, g, dim3(256), 0, s, (float *)out,
-                           (const float *)in, map, n);
-      else
-        hipLaunchKernelGGL(k_permute_out<float>, g, dim3(256), 0, s, (float *)out,
-                           (const float *)in, map, n);
-    }
+  with_real(ts == 8 ? GLS_F64 : GLS_F32, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(in_dir ? k_permute_in<T> : k_permute_out<T>, g, dim3(256), 0, s, (T *)out,
+                       (const T *)in, map, n);
+  });
   HIP_THROW(hipGetLastError());
 }
 
@@ -1635,23 +1511,6 @@ max_u_t(const glsOp_ *op, const void *vec, hipStream_t s)
   HIP_THROW(hipFreeAsync(part, s));
   HIP_THROW(hipStreamSynchronize(s));
   return r;
-}
-
-template <typename T>
-double
-max_u_p(const glsOp_ *op, const void *vec, hipStream_t s)
-{
-#define GLS_CASE(D, K)              \
-  if (op->dim == D && op->degree == K) \
-    return max_u_t<D, K, T>(op, vec, s);
-  GLS_CASE(2, 1)
-  GLS_CASE(2, 2)
-  GLS_CASE(2, 3)
-  GLS_CASE(3, 1)
-  GLS_CASE(3, 2)
-  GLS_CASE(3, 3)
-#undef GLS_CASE
-  throw std::runtime_error("get_max_u: no instantiation for this (dim, degree)");
 }
 } // namespace
 
@@ -2026,39 +1885,21 @@ gls_op_create(const glsOpDesc *d, glsOp *out)
             }
         }
     }
-  if (op->prec == GLS_F64)
+  if (op->use_brick)
     {
-      if (op->use_brick)
-        {
-          upload(&op->d_bgeo_cart, bcart);
-          upload(&op->d_bgeo_gen, bgen);
-        }
-      upload(&op->d_geo_cart, cart);
-      upload(&op->d_geo_gen, gen);
-      upload(&op->d_hq, hq);
-      upload(&op->d_hmin, hmin);
+      upload_real(op->prec, &op->d_bgeo_cart, bcart);
+      upload_real(op->prec, &op->d_bgeo_gen, bgen);
     }
-  else
-    {
-      if (op->use_brick)
-        {
-          upload(&op->d_bgeo_cart, convert<float>(bcart));
-          upload(&op->d_bgeo_gen, convert<float>(bgen));
-        }
-      upload(&op->d_geo_cart, convert<float>(cart));
-      upload(&op->d_geo_gen, convert<float>(gen));
-      upload(&op->d_hq, convert<float>(hq));
-      upload(&op->d_hmin, convert<float>(hmin));
-    }
+  upload_real(op->prec, &op->d_geo_cart, cart);
+  upload_real(op->prec, &op->d_geo_gen, gen);
+  upload_real(op->prec, &op->d_hq, hq);
+  upload_real(op->prec, &op->d_hmin, hmin);
   const size_t ts = op->tsize();
   build_table_layout(op);
   if (op->use_brick)
-    {
-      if (op->prec == GLS_F64)
-        upload(&op->d_coef_image, coef_image<double>(op->basis, n));
-      else
-        upload(&op->d_coef_image, coef_image<float>(op->basis, n));
-    }
+    with_real(op->prec, [&](auto t) {
+      upload(&op->d_coef_image, coef_image<decltype(t)>(op->basis, n));
+    });
   HIP_THROW(hipMalloc(&op->d_tab, std::max<size_t>(1, (size_t)op->tab_elems * ts)));
   HIP_THROW(hipMemset(op->d_tab, 0, std::max<size_t>(1, (size_t)op->tab_elems * ts)));
   HIP_THROW(hipMalloc(&op->d_cellwise, std::max<size_t>(1, 2 * (size_t)d->n_cells * ts)));
@@ -2149,12 +1990,9 @@ gls_op_set_linearization_point(glsOp op, const void *vec, void *stream)
   gls::Section sec_("ns::set_linearization_point", (hipStream_t)stream);
   if (!op || !vec)
     throw std::runtime_error("gls_op_set_linearization_point: null argument");
-  ApplyFn     af;
-  ProduceFn   pf;
   hipStream_t s = (hipStream_t)stream;
-  select(op, af, pf);
   const void *x = op->stage.in_vec(vec, 0, s);
-  pf(op, 0, x, s);
+  produce(op, 0, x, s);
   gls::faces_linearization(op, x, s);
   op->stage.done(s);
   op->have_lin = true;
@@ -2177,10 +2015,7 @@ gls_op_set_previous_solution(glsOp op, const void *const *hist, int n_hist,
     return 0; // operator_ns.cc:243-244
   if (!hist || !weights || n_hist < order + 1 || order > 3)
     throw std::runtime_error("gls_op_set_previous_solution: need order+1 history vectors");
-  ApplyFn     af;
-  ProduceFn   pf;
   hipStream_t s = (hipStream_t)stream;
-  select(op, af, pf);
   const void *x[4] = {nullptr, nullptr, nullptr, nullptr};
   double      w[4] = {0, 0, 0, 0};
   for (int i = 1; i <= order; ++i)
@@ -2190,18 +2025,14 @@ gls_op_set_previous_solution(glsOp op, const void *const *hist, int n_hist,
       x[i - 1] = op->stage.in_vec(hist[i], i - 1, s);
       w[i - 1] = weights[i];
     }
-  if (op->prec == GLS_F64)
-    hipLaunchKernelGGL(k_lincomb<double>, grid1d(op->n_dofs), dim3(256), 0, s,
-                       (double *)op->d_tmp, (const double *)x[0], (const double *)x[1],
-                       (const double *)x[2], (const double *)x[3], w[0], w[1], w[2], w[3],
-                       op->n_dofs);
-  else
-    hipLaunchKernelGGL(k_lincomb<float>, grid1d(op->n_dofs), dim3(256), 0, s,
-                       (float *)op->d_tmp, (const float *)x[0], (const float *)x[1],
-                       (const float *)x[2], (const float *)x[3], w[0], w[1], w[2], w[3],
-                       op->n_dofs);
+  with_real(op->prec, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_lincomb<T>, grid1d(op->n_dofs), dim3(256), 0, s, (T *)op->d_tmp,
+                       (const T *)x[0], (const T *)x[1], (const T *)x[2], (const T *)x[3], w[0],
+                       w[1], w[2], w[3], op->n_dofs);
+  });
   HIP_THROW(hipGetLastError());
-  pf(op, 1, op->d_tmp, s);
+  produce(op, 1, op->d_tmp, s);
   op->have_prev = true;
   op->t1_valid  = false;
   op->version++;
@@ -2213,7 +2044,7 @@ gls_op_set_previous_solution(glsOp op, const void *const *hist, int n_hist,
           const size_t sz = (size_t)(op->dim * op->dim + op->dim) * op->n_cells * op->nq * op->tsize();
           HIP_THROW(hipMalloc(&op->d_old_grad, std::max<size_t>(1, sz)));
         }
-      pf(op, 2, x[0], s);
+      produce(op, 2, x[0], s);
       op->have_old_grad = true;
     }
   op->stage.done(s);
@@ -2239,12 +2070,11 @@ gls_op_apply_identity_rows(glsOp op, void *dst, const void *src, void *stream)
   if (op->n_owned_dofs == 0)
     return 0;
   hipStream_t s = (hipStream_t)stream;
-  if (op->prec == GLS_F64)
-    hipLaunchKernelGGL(k_identity_rows<double>, grid1d(op->n_owned_dofs), dim3(256), 0, s,
-                       (double *)dst, (const double *)src, op->d_cbits, op->n_owned_dofs);
-  else
-    hipLaunchKernelGGL(k_identity_rows<float>, grid1d(op->n_owned_dofs), dim3(256), 0, s,
-                       (float *)dst, (const float *)src, op->d_cbits, op->n_owned_dofs);
+  with_real(op->prec, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_identity_rows<T>, grid1d(op->n_owned_dofs), dim3(256), 0, s, (T *)dst,
+                       (const T *)src, op->d_cbits, op->n_owned_dofs);
+  });
   HIP_THROW(hipGetLastError());
   GLS_CATCH
 }
@@ -2264,10 +2094,9 @@ gls_op_vmult_cells(glsOp op, void *dst, const void *src, int64_t b, int64_t e, v
   if (op->nc.n)
     throw std::runtime_error("gls_op_vmult_cells: operators with node constraints are not "
                              "supported, they run gls_op_vmult");
-  ApplyFn   af;
-  ProduceFn pf;
-  select(op, af, pf);
-  af(op, vmult_mode(op), false, dst, src, b, e, (hipStream_t)stream);
+  with_impl(op, "gls_op_vmult_cells", [&](auto impl) {
+    decltype(impl)::apply(op, vmult_mode(op), false, dst, src, b, e, (hipStream_t)stream);
+  });
   GLS_CATCH
 }
 
@@ -2357,14 +2186,11 @@ static void
 distribute(glsOp op, void *tmp, const void *src, hipStream_t s)
 {
   const int nc = op->dim + 1;
-  if (op->prec == GLS_F64)
-    hipLaunchKernelGGL(k_distribute<double>, grid1d(op->n_dofs), dim3(256), 0, s,
-                       (double *)tmp, (const double *)src, op->d_node_cmask,
-                       (const double *)op->d_inhom, op->n_dofs, nc);
-  else
-    hipLaunchKernelGGL(k_distribute<float>, grid1d(op->n_dofs), dim3(256), 0, s, (float *)tmp,
-                       (const float *)src, op->d_node_cmask, (const float *)op->d_inhom,
-                       op->n_dofs, nc);
+  with_real(op->prec, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_distribute<T>, grid1d(op->n_dofs), dim3(256), 0, s, (T *)tmp,
+                       (const T *)src, op->d_node_cmask, (const T *)op->d_inhom, op->n_dofs, nc);
+  });
   HIP_THROW(hipGetLastError());
 }
 
@@ -2422,17 +2248,16 @@ gls_op_set_constraint_values(glsOp op, const void *values, void *stream)
 static void
 residual_cells(glsOp op, void *dst, const void *src, hipStream_t s)
 {
-  ApplyFn   af;
-  ProduceFn pf;
-  select(op, af, pf);
-  if (op->use_brick)
-    select_brick(op)(op, MODE_RESIDUAL, dst, src, 0, op->n_bricks, BRICK_RUN | BRICK_REDUCE,
-                     s, nullptr);
-  else
-    {
-      HIP_THROW(hipMemsetAsync(dst, 0, (size_t)op->n_dofs * op->tsize(), s));
-      af(op, MODE_RESIDUAL, false, dst, src, 0, op->n_cells, s);
-    }
+  with_impl(op, "evaluate_residual", [&](auto impl) {
+    using I = decltype(impl);
+    if (op->use_brick)
+      I::brick(op, MODE_RESIDUAL, dst, src, 0, op->n_bricks, BRICK_RUN | BRICK_REDUCE, s, nullptr);
+    else
+      {
+        HIP_THROW(hipMemsetAsync(dst, 0, (size_t)op->n_dofs * op->tsize(), s));
+        I::apply(op, MODE_RESIDUAL, false, dst, src, 0, op->n_cells, s);
+      }
+  });
   gls::faces_apply(op, true, dst, src, s);
 }
 
@@ -2508,7 +2333,11 @@ gls_op_get_max_u(glsOp op, const void *vec, double *u_max, void *stream)
     throw std::runtime_error("gls_op_get_max_u: null argument");
   hipStream_t s = (hipStream_t)stream;
   const void *x = op->stage.in_vec(vec, 0, s);
-  *u_max        = op->prec == GLS_F64 ? max_u_p<double>(op, x, s) : max_u_p<float>(op, x, s);
+  *u_max        = with_real(op->prec, [&](auto t) {
+    return with_dim_degree(op->dim, op->degree, "get_max_u", [&](auto d, auto k) {
+      return max_u_t<decltype(d)::value, decltype(k)::value, decltype(t)>(op, x, s);
+    });
+  });
   GLS_CATCH
 }
 
@@ -2524,16 +2353,15 @@ gls_op_compute_diagonal(glsOp op, void *diag, void *stream)
   double     *d64 = nullptr;
   HIP_THROW(hipMallocAsync((void **)&d64, (size_t)op->n_dofs * sizeof(double), s));
   HIP_THROW(hipMemsetAsync(d64, 0, (size_t)op->n_dofs * sizeof(double), s));
-  (op->prec == GLS_F64 ? select_diag_t<double>(op->dim, op->degree) :
-                         select_diag_t<float>(op->dim, op->degree))(op, vmult_mode(op), d64, s);
+  with_impl(op, "compute_diagonal",
+            [&](auto impl) { decltype(impl)::diag(op, vmult_mode(op), d64, s); });
   gls::faces_diagonal(op, d64, true, s);
   gls::nc_diagonal(op, d64, vmult_unwrapped, s);
-  if (op->prec == GLS_F64)
-    hipLaunchKernelGGL(k_diag_out<double>, grid1d(op->n_dofs), dim3(256), 0, s, (double *)diag,
+  with_real(op->prec, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_diag_out<T>, grid1d(op->n_dofs), dim3(256), 0, s, (T *)diag,
                        (const double *)d64, op->d_cbits, op->n_owned_dofs, op->n_dofs);
-  else
-    hipLaunchKernelGGL(k_diag_out<float>, grid1d(op->n_dofs), dim3(256), 0, s, (float *)diag,
-                       (const double *)d64, op->d_cbits, op->n_owned_dofs, op->n_dofs);
+  });
   HIP_THROW(hipGetLastError());
   HIP_THROW(hipFreeAsync(d64, s));
   GLS_CATCH
@@ -2546,12 +2374,11 @@ gls_op_invert_diagonal(glsOp op, void *diag, void *stream)
   if (!op || !diag)
     throw std::runtime_error("gls_op_invert_diagonal: null argument");
   hipStream_t s = (hipStream_t)stream;
-  if (op->prec == GLS_F64)
-    hipLaunchKernelGGL(k_invert_diag<double>, grid1d(op->n_dofs), dim3(256), 0, s,
-                       (double *)diag, op->d_cbits, op->n_owned_dofs, op->n_dofs);
-  else
-    hipLaunchKernelGGL(k_invert_diag<float>, grid1d(op->n_dofs), dim3(256), 0, s, (float *)diag,
+  with_real(op->prec, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_invert_diag<T>, grid1d(op->n_dofs), dim3(256), 0, s, (T *)diag,
                        op->d_cbits, op->n_owned_dofs, op->n_dofs);
+  });
   HIP_THROW(hipGetLastError());
   GLS_CATCH
 }
@@ -2627,21 +2454,17 @@ op_inverse_diagonal_device(glsOp op, void *diag, hipStream_t s)
       if (op->prec != GLS_F64)
         HIP_THROW(hipMallocAsync((void **)&d64, (size_t)op->n_dofs * sizeof(double), s));
       HIP_THROW(hipMemsetAsync(d64, 0, (size_t)op->n_dofs * sizeof(double), s));
-      (op->prec == GLS_F64 ? select_diag_t<double>(op->dim, op->degree) :
-                             select_diag_t<float>(op->dim, op->degree))(op, vmult_mode(op), d64, s);
+      with_impl(op, "compute_inverse_diagonal",
+                [&](auto impl) { decltype(impl)::diag(op, vmult_mode(op), d64, s); });
       faces_diagonal(op, d64, true, s);
       nc_diagonal(op, d64, vmult_unwrapped, s);
-      if (op->prec == GLS_F64)
-        hipLaunchKernelGGL(k_invert_diag64<double>, grid1d(op->n_dofs), dim3(256), 0, s,
-                           (double *)diag, (const double *)d64, op->d_cbits, op->n_owned_dofs,
-                           op->n_dofs);
-      else
-        {
-          hipLaunchKernelGGL(k_invert_diag64<float>, grid1d(op->n_dofs), dim3(256), 0, s,
-                             (float *)diag, (const double *)d64, op->d_cbits, op->n_owned_dofs,
-                             op->n_dofs);
-          HIP_THROW(hipFreeAsync(d64, s));
-        }
+      with_real(op->prec, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(k_invert_diag64<T>, grid1d(op->n_dofs), dim3(256), 0, s, (T *)diag,
+                           (const double *)d64, op->d_cbits, op->n_owned_dofs, op->n_dofs);
+      });
+      if (op->prec != GLS_F64)
+        HIP_THROW(hipFreeAsync(d64, s));
       HIP_THROW(hipGetLastError());
     }
 }
@@ -2651,11 +2474,9 @@ op_element_matrices_device(const glsOp_ *op, void *emat, int64_t b, int64_t e, h
 {
   if (!op->have_lin)
     throw std::runtime_error("element matrices before set_linearization_point");
-  EmatFn fn = op->prec == GLS_F64 ? select_emat_t<double>(op->dim, op->degree) :
-                                    select_emat_t<float>(op->dim, op->degree);
-  if (!fn)
-    throw std::runtime_error("no kernel instantiation for this (dim, degree)");
-  fn(op, vmult_mode(op), emat, b, e, s);
+  with_impl(op, "element matrices", [&](auto impl) {
+    decltype(impl)::element_matrices(op, vmult_mode(op), emat, b, e, s);
+  });
   faces_element_matrices(op, emat, b, e, s);
 }
 } // namespace gls
@@ -2681,18 +2502,8 @@ gls_op_upload_tables(glsOp op, const double *tables, const double *cellwise)
         cw[c]               = cellwise[2 * ext_cell(op, c)];
         cw[op->n_cells + c] = cellwise[2 * ext_cell(op, c) + 1];
       }
-  if (op->prec == GLS_F64)
-    {
-      HIP_THROW(hipMemcpy(op->d_tab, soa.data(), soa.size() * 8, hipMemcpyHostToDevice));
-      HIP_THROW(hipMemcpy(op->d_cellwise, cw.data(), cw.size() * 8, hipMemcpyHostToDevice));
-    }
-  else
-    {
-      auto sf = convert<float>(soa);
-      auto cf = convert<float>(cw);
-      HIP_THROW(hipMemcpy(op->d_tab, sf.data(), sf.size() * 4, hipMemcpyHostToDevice));
-      HIP_THROW(hipMemcpy(op->d_cellwise, cf.data(), cf.size() * 4, hipMemcpyHostToDevice));
-    }
+  upload_real(op->prec, &op->d_tab, soa, false);
+  upload_real(op->prec, &op->d_cellwise, cw, false);
   op->have_lin  = true;
   op->have_prev = op->prm.order > 0;
   // the H field from the cell geometry (the uploaded tables carry delta only)
@@ -2701,18 +2512,14 @@ gls_op_upload_tables(glsOp op, const double *tables, const double *cellwise)
     const dim3    g((unsigned)((nqc + 255) / 256));
     if (nqc > 0)
       {
-        if (op->prec == GLS_F64 && op->dim == 3)
-          hipLaunchKernelGGL((k_fill_h<3, double>), g, dim3(256), 0, 0, (double *)op->d_tab,
-                             op->d_tab_cbase, op->tab_gs, (const double *)op->d_hq, op->n_cells, op->nq);
-        else if (op->prec == GLS_F64)
-          hipLaunchKernelGGL((k_fill_h<2, double>), g, dim3(256), 0, 0, (double *)op->d_tab,
-                             op->d_tab_cbase, op->tab_gs, (const double *)op->d_hq, op->n_cells, op->nq);
-        else if (op->dim == 3)
-          hipLaunchKernelGGL((k_fill_h<3, float>), g, dim3(256), 0, 0, (float *)op->d_tab,
-                             op->d_tab_cbase, op->tab_gs, (const float *)op->d_hq, op->n_cells, op->nq);
-        else
-          hipLaunchKernelGGL((k_fill_h<2, float>), g, dim3(256), 0, 0, (float *)op->d_tab,
-                             op->d_tab_cbase, op->tab_gs, (const float *)op->d_hq, op->n_cells, op->nq);
+        with_real(op->prec, [&](auto t) {
+          using T = decltype(t);
+          with_int<2, 3>(op->dim, "gls_op_upload_tables", [&](auto d) {
+            hipLaunchKernelGGL((k_fill_h<decltype(d)::value, T>), g, dim3(256), 0, 0,
+                               (T *)op->d_tab, op->d_tab_cbase, op->tab_gs, (const T *)op->d_hq,
+                               op->n_cells, op->nq);
+          });
+        });
         HIP_THROW(hipGetLastError());
         HIP_THROW(hipDeviceSynchronize());
       }
@@ -2731,19 +2538,14 @@ gls_op_download_tables(glsOp op, double *tables, double *cellwise)
     throw std::runtime_error("gls_op_download_tables: null argument");
   HIP_THROW(hipDeviceSynchronize());
   std::vector<double> soa((size_t)op->tab_elems), cw((size_t)2 * op->n_cells);
-  if (op->prec == GLS_F64)
-    {
-      HIP_THROW(hipMemcpy(soa.data(), op->d_tab, soa.size() * 8, hipMemcpyDeviceToHost));
-      HIP_THROW(hipMemcpy(cw.data(), op->d_cellwise, cw.size() * 8, hipMemcpyDeviceToHost));
-    }
-  else
-    {
-      std::vector<float> sf(soa.size()), cf(cw.size());
-      HIP_THROW(hipMemcpy(sf.data(), op->d_tab, sf.size() * 4, hipMemcpyDeviceToHost));
-      HIP_THROW(hipMemcpy(cf.data(), op->d_cellwise, cf.size() * 4, hipMemcpyDeviceToHost));
-      soa.assign(sf.begin(), sf.end());
-      cw.assign(cf.begin(), cf.end());
-    }
+  with_real(op->prec, [&](auto t) {
+    using T = decltype(t);
+    std::vector<T> st(soa.size()), ct(cw.size());
+    HIP_THROW(hipMemcpy(st.data(), op->d_tab, st.size() * sizeof(T), hipMemcpyDeviceToHost));
+    HIP_THROW(hipMemcpy(ct.data(), op->d_cellwise, ct.size() * sizeof(T), hipMemcpyDeviceToHost));
+    soa.assign(st.begin(), st.end());
+    cw.assign(ct.begin(), ct.end());
+  });
   if (tables)
     for (int64_t c = 0; c < op->n_cells; ++c)
       for (int q = 0; q < op->nq; ++q)
@@ -2791,33 +2593,22 @@ element_matrices_host(glsOp op, double *out)
   const int     ndof  = op->nq * (op->dim + 1);
   const size_t  per   = (size_t)ndof * ndof;
   const int64_t chunk = std::max<int64_t>(1, (int64_t)((256u << 20) / (per * op->tsize())));
-  EmatFn        fn    = op->prec == GLS_F64 ? select_emat_t<double>(op->dim, op->degree) :
-                                              select_emat_t<float>(op->dim, op->degree);
-  if (!fn)
-    throw std::runtime_error("no kernel instantiation for this (dim, degree)");
   void *buf = nullptr;
   HIP_THROW(hipMalloc(&buf, (size_t)std::min(chunk, op->n_cells) * per * op->tsize()));
   std::vector<double> tmp;
-  std::vector<float>  tmpf;
   try
     {
       for (int64_t b = 0; b < op->n_cells; b += chunk)
         {
           const int64_t e = std::min(op->n_cells, b + chunk);
-          fn(op, op_vmult_mode(op), buf, b, e, nullptr);
-          faces_element_matrices(op, buf, b, e, nullptr);
+          op_element_matrices_device(op, buf, b, e, nullptr);
           const size_t cnt = (size_t)(e - b) * per;
-          if (op->prec == GLS_F64)
-            {
-              tmp.resize(cnt);
-              HIP_THROW(hipMemcpy(tmp.data(), buf, cnt * 8, hipMemcpyDeviceToHost));
-            }
-          else
-            {
-              tmpf.resize(cnt);
-              HIP_THROW(hipMemcpy(tmpf.data(), buf, cnt * 4, hipMemcpyDeviceToHost));
-              tmp.assign(tmpf.begin(), tmpf.end());
-            }
+          with_real(op->prec, [&](auto t) {
+            using T = decltype(t);
+            std::vector<T> tt(cnt);
+            HIP_THROW(hipMemcpy(tt.data(), buf, cnt * sizeof(T), hipMemcpyDeviceToHost));
+            tmp.assign(tt.begin(), tt.end());
+          });
           for (int64_t c = b; c < e; ++c)
             std::copy(tmp.begin() + (size_t)(c - b) * per, tmp.begin() + (size_t)(c - b + 1) * per,
                       out + (size_t)ext_cell(op, c) * per);

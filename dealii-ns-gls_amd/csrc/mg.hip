@@ -455,15 +455,6 @@ k_copy(uint32_t *__restrict__ y, const uint32_t *__restrict__ x, int64_t n_words
     y[i] = x[i];
 }
 
-template <typename Tin, typename Tout>
-__global__ void
-k_convert(Tout *__restrict__ dst, const Tin *__restrict__ src, int64_t n)
-{
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n)
-    dst[i] = (Tout)src[i];
-}
-
 // power iteration step (deal.II power_iteration, see power_iteration_t):
 // y = D^{-1} (A x) in place; per-block partial sums of x.y and y.y into
 // part[2 block], part[2 block + 1] (no atomics: k_power_finish adds the
@@ -797,26 +788,6 @@ transfer_t(const glsMG_ *mg, int kind, int level, void *dst, const void *src, hi
   HIP_THROW(hipGetLastError());
 }
 
-template <typename T>
-void
-transfer_p(const glsMG_ *mg, int kind, int level, void *dst, const void *src, hipStream_t s,
-           const void *base)
-{
-  // the coarse level's degree: a FE_Q_iso_Q1 coarsest level is Q1 on the
-  // sub-cells under Q_k levels (main.cc:436-446)
-  const int d = mg->dim, k = mg->ops[level - 1]->degree;
-  if (d == 2 && k == 1)
-    transfer_t<2, 1, T>(mg, kind, level, dst, src, s, base);
-  else if (d == 2 && k == 2)
-    transfer_t<2, 2, T>(mg, kind, level, dst, src, s, base);
-  else if (d == 3 && k == 1)
-    transfer_t<3, 1, T>(mg, kind, level, dst, src, s, base);
-  else if (d == 3 && k == 2)
-    transfer_t<3, 2, T>(mg, kind, level, dst, src, s, base);
-  else
-    throw std::runtime_error("multigrid transfer: degree must be 1 or 2");
-}
-
 void
 transfer(const glsMG_ *mg, int kind, int level, void *dst, const void *src, hipStream_t s,
          const void *base = nullptr)
@@ -830,10 +801,17 @@ transfer(const glsMG_ *mg, int kind, int level, void *dst, const void *src, hipS
   const glsOp_ *cop = mg->ops[level - 1];
   if (kind == 0)
     gls::nc_resolve(cop, const_cast<void *>(src), true, s);
-  if (mg->prec == GLS_F64)
-    transfer_p<double>(mg, kind, level, dst, src, s, base);
-  else
-    transfer_p<float>(mg, kind, level, dst, src, s, base);
+  // the coarse level's degree: a FE_Q_iso_Q1 coarsest level is Q1 on the
+  // sub-cells under Q_k levels (main.cc:436-446)
+  const int k = cop->degree;
+  if (k != 1 && k != 2)
+    throw std::runtime_error("multigrid transfer: degree must be 1 or 2");
+  gls::with_real(mg->prec, [&](auto t) {
+    gls::with_dim_degree<2>(mg->dim, k, "multigrid transfer", [&](auto d, auto kk) {
+      transfer_t<decltype(d)::value, decltype(kk)::value, decltype(t)>(mg, kind, level, dst, src,
+                                                                         s, base);
+    });
+  });
   if (kind == 0)
     gls::nc_restore(cop, const_cast<void *>(src), s);
   else if (kind == 1)
@@ -847,14 +825,17 @@ check(glsStatus st)
     throw std::runtime_error(gls_last_error());
 }
 
-template <typename T>
+// x = omega D^{-1} b (first) or x += omega D^{-1} (b - tmp[level])
 void
-relax_t(const glsMG_ *mg, int level, void *x, const void *b, int first, hipStream_t s)
+relax(const glsMG_ *mg, int level, void *x, const void *b, int first, hipStream_t s)
 {
   const int64_t n = mg->ops[level]->n_dofs;
-  hipLaunchKernelGGL(k_relax<T>, g1(n), dim3(256), 0, s, (T *)x, (const T *)b,
-                     (const T *)mg->tmp[level], (const T *)mg->invdiag[level],
-                     (T)mg->omega[level], first, n);
+  gls::with_real(mg->prec, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_relax<T>, g1(n), dim3(256), 0, s, (T *)x, (const T *)b,
+                       (const T *)mg->tmp[level], (const T *)mg->invdiag[level],
+                       (T)mg->omega[level], first, n);
+  });
   HIP_THROW(hipGetLastError());
 }
 
@@ -866,14 +847,16 @@ struct FirstRelax
   const double *b64        = nullptr; // FP64 defect to convert into b
 };
 
-template <typename T>
 void
-relax_first_t(const glsMG_ *mg, int level, void *x, void *b, const FirstRelax &fr, hipStream_t s)
+relax_first(const glsMG_ *mg, int level, void *x, void *b, const FirstRelax &fr, hipStream_t s)
 {
   const int64_t n = mg->ops[level]->n_dofs;
-  hipLaunchKernelGGL(k_relax_first<T>, g1(std::max(n, fr.zero_words)), dim3(256), 0, s, (T *)x,
-                     (const T *)b, (const T *)mg->invdiag[level], (T)mg->omega[level], n,
-                     fr.zero, fr.zero_words, fr.b64, (T *)b);
+  gls::with_real(mg->prec, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_relax_first<T>, g1(std::max(n, fr.zero_words)), dim3(256), 0, s, (T *)x,
+                       (const T *)b, (const T *)mg->invdiag[level], (T)mg->omega[level], n,
+                       fr.zero, fr.zero_words, fr.b64, (T *)b);
+  });
   HIP_THROW(hipGetLastError());
 }
 
@@ -923,11 +906,9 @@ smooth(const glsMG_ *mg, int level, void *x, const void *b, bool zero_start, int
        hipStream_t s, bool start_in_tmp = false, const FirstRelax *fr = nullptr,
        PendingReduce *pend = nullptr, double *out64 = nullptr, bool *wrote64 = nullptr)
 {
-  auto  relax = mg->prec == GLS_F64 ? relax_t<double> : relax_t<float>;
   auto  first = [&](void *xx) {
     if (fr)
-      (mg->prec == GLS_F64 ? relax_first_t<double> : relax_first_t<float>)(mg, level, xx,
-                                                                          (void *)b, *fr, s);
+      relax_first(mg, level, xx, (void *)b, *fr, s);
     else
       relax(mg, level, xx, b, 1, s);
   };
@@ -1047,12 +1028,10 @@ void
 residual(const glsMG_ *mg, int level, void *t, const void *b, hipStream_t s)
 {
   const int64_t n = mg->ops[level]->n_dofs;
-  if (mg->prec == GLS_F64)
-    hipLaunchKernelGGL(k_residual<double>, g1(n), dim3(256), 0, s, (double *)t,
-                       (const double *)b, n);
-  else
-    hipLaunchKernelGGL(k_residual<float>, g1(n), dim3(256), 0, s, (float *)t,
-                       (const float *)b, n);
+  gls::with_real(mg->prec, [&](auto r) {
+    using T = decltype(r);
+    hipLaunchKernelGGL(k_residual<T>, g1(n), dim3(256), 0, s, (T *)t, (const T *)b, n);
+  });
   HIP_THROW(hipGetLastError());
 }
 
@@ -2120,45 +2099,31 @@ void
 coarse_apply(glsMG_ *mg, hipStream_t s, PendingReduce *pend = nullptr)
 {
   const size_t bytes = (size_t)mg->ops[0]->n_dofs * mg->ts();
-  if (mg->coarse_ilu)
+  if (mg->coarse_ilu || mg->desc.coarse_amg)
     {
-      // the ILU factor once (coarse_iterate = 0): in FP64
-      const int64_t n = mg->ops[0]->n_dofs;
+      // the ILU factor, or one AMG V-cycle, once (coarse_iterate = 0): in
+      // FP64, FP32 levels converted through amg_io
+      const int64_t n     = mg->ops[0]->n_dofs;
+      auto          apply = [&](double *y, const double *x) {
+        if (mg->coarse_ilu)
+          check_ilu(gls_ilu_vmult(mg->ilu, y, x, s));
+        else
+          check_amg(gls_amg_vmult(mg->amg, y, x, s));
+      };
       if (mg->prec == GLS_F64)
-        check_ilu(gls_ilu_vmult(mg->ilu, (double *)mg->sol[0], (const double *)mg->def[0], s));
+        apply((double *)mg->sol[0], (const double *)mg->def[0]);
       else
         {
           hipLaunchKernelGGL((k_convert<float, double>), g1(n), dim3(256), 0, s, mg->amg_io,
                              (const float *)mg->def[0], n);
-          check_ilu(gls_ilu_vmult(mg->ilu, mg->amg_io + n, mg->amg_io, s));
-          hipLaunchKernelGGL((k_convert<double, float>), g1(n), dim3(256), 0, s,
-                             (float *)mg->sol[0], mg->amg_io + n, n);
-        }
-      HIP_THROW(hipGetLastError());
-    }
-  else if (mg->desc.coarse_amg)
-    {
-      // one AMG V-cycle as the coarse solver (coarse_iterate = 0): in FP64
-      const int64_t n = mg->ops[0]->n_dofs;
-      if (mg->prec == GLS_F64)
-        check_amg(gls_amg_vmult(mg->amg, (double *)mg->sol[0], (const double *)mg->def[0], s));
-      else
-        {
-          hipLaunchKernelGGL((k_convert<float, double>), g1(n), dim3(256), 0, s, mg->amg_io,
-                             (const float *)mg->def[0], n);
-          check_amg(gls_amg_vmult(mg->amg, mg->amg_io + n, mg->amg_io, s));
+          apply(mg->amg_io + n, mg->amg_io);
           hipLaunchKernelGGL((k_convert<double, float>), g1(n), dim3(256), 0, s,
                              (float *)mg->sol[0], mg->amg_io + n, n);
         }
       HIP_THROW(hipGetLastError());
     }
   else if (mg->desc.coarse_n_iterations < 0)
-    {
-      if (mg->prec == GLS_F64)
-        coarse_lu_solve_t<double>(mg, s);
-      else
-        coarse_lu_solve_t<float>(mg, s);
-    }
+    gls::with_real(mg->prec, [&](auto t) { coarse_lu_solve_t<decltype(t)>(mg, s); });
   else if (mg->desc.coarse_n_iterations == 0)
     {
       copy_words(mg->sol[0], mg->def[0], (int64_t)(bytes / 4), s);
@@ -2345,10 +2310,7 @@ v_step_body(glsMG_ *mg, int l, hipStream_t s)
   if (l == 0 && mg->desc.coarse_iterate)
     {
       gls::Section sc(sec[5], s);
-      if (mg->prec == GLS_F64)
-        coarse_gmres_t<double>(mg, s);
-      else
-        coarse_gmres_t<float>(mg, s);
+      gls::with_real(mg->prec, [&](auto t) { coarse_gmres_t<decltype(t)>(mg, s); });
       return;
     }
   // the last smoothing step's reduction of a level below the finest handed
@@ -2640,14 +2602,7 @@ gls_mg_create(const glsMGDesc *desc, const glsOp *levels, const uint32_t *const 
       HIP_THROW(hipMemcpy(mg->d_child[l], ch.data(), nch * sizeof(uint32_t),
                           hipMemcpyHostToDevice));
       mg->h_weight[l] = w;
-      HIP_THROW(hipMalloc(&mg->d_weight[l], w.size() * mg->ts()));
-      if (mg->prec == GLS_F64)
-        HIP_THROW(hipMemcpy(mg->d_weight[l], w.data(), w.size() * 8, hipMemcpyHostToDevice));
-      else
-        {
-          std::vector<float> wf(w.begin(), w.end());
-          HIP_THROW(hipMemcpy(mg->d_weight[l], wf.data(), wf.size() * 4, hipMemcpyHostToDevice));
-        }
+      gls::upload_real(mg->prec, &mg->d_weight[l], w);
     }
   for (int l = 0; l < nl_levels; ++l)
     {
@@ -2764,13 +2719,7 @@ gls_mg_setup(glsMG mg, void *stream)
       std::vector<double> w = mg->h_weight[l];
       for (int64_t i = 0; i < fop->nc.n; ++i)
         w[(size_t)(fop->nc.h_node[(size_t)i] * mg->nc + fop->nc.h_comp[(size_t)i])] = 0.0;
-      if (mg->prec == GLS_F64)
-        HIP_THROW(hipMemcpy(mg->d_weight[l], w.data(), w.size() * 8, hipMemcpyHostToDevice));
-      else
-        {
-          std::vector<float> wf(w.begin(), w.end());
-          HIP_THROW(hipMemcpy(mg->d_weight[l], wf.data(), wf.size() * 4, hipMemcpyHostToDevice));
-        }
+      gls::upload_real(mg->prec, &mg->d_weight[l], w, false);
       mg->weight_nc_version[l] = fop->nc_version;
     }
   // every allocation and launch of the setup (the AMG hierarchy included)
@@ -2833,10 +2782,8 @@ gls_mg_setup(glsMG mg, void *stream)
       else
         {
           gls::Section sc("gmg::initialize::smoother::init1", ls);
-          if (mg->prec == GLS_F64)
-            power_iteration_t<double>(mg, (int)l, ls);
-          else
-            power_iteration_t<float>(mg, (int)l, ls);
+          gls::with_real(mg->prec,
+                         [&](auto t) { power_iteration_t<decltype(t)>(mg, (int)l, ls); });
           estimate[l] = 1;
         }
       HIP_THROW(hipMemsetAsync(mg->sol[l], 0, (size_t)mg->ops[l]->n_dofs * mg->ts(), ls));
@@ -2939,10 +2886,7 @@ gls_mg_setup(glsMG mg, void *stream)
   else if (mg->desc.coarse_n_iterations < 0)
     {
       gls::Section sc("gmg::initialize::direct", s);
-      if (mg->prec == GLS_F64)
-        coarse_lu_setup_t<double>(mg, s);
-      else
-        coarse_lu_setup_t<float>(mg, s);
+      gls::with_real(mg->prec, [&](auto t) { coarse_lu_setup_t<decltype(t)>(mg, s); });
     }
   HIP_THROW(hipStreamSynchronize(s));
   mg->setup_done = true;
@@ -3053,14 +2997,11 @@ gls_mg_relax(glsMG mg, int level, void *x, const void *b, const void *ax, const 
     throw std::runtime_error("gls_mg_relax: bad arguments");
   const int64_t n = mg->ops[level]->n_dofs;
   hipStream_t   s = (hipStream_t)stream;
-  if (mg->prec == GLS_F64)
-    hipLaunchKernelGGL(k_relax<double>, g1(n), dim3(256), 0, s, (double *)x, (const double *)b,
-                       (const double *)ax, (const double *)inv_diag, omega, zero_start ? 1 : 0,
-                       n);
-  else
-    hipLaunchKernelGGL(k_relax<float>, g1(n), dim3(256), 0, s, (float *)x, (const float *)b,
-                       (const float *)ax, (const float *)inv_diag, (float)omega,
-                       zero_start ? 1 : 0, n);
+  gls::with_real(mg->prec, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_relax<T>, g1(n), dim3(256), 0, s, (T *)x, (const T *)b, (const T *)ax,
+                       (const T *)inv_diag, (T)omega, zero_start ? 1 : 0, n);
+  });
   HIP_THROW(hipGetLastError());
   GLS_CATCH
 }

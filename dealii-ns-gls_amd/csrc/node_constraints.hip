@@ -264,37 +264,6 @@ __global__ void __launch_bounds__(NC_BLOCK)
 
 template <typename T>
 void
-resolve_t(const glsOp_ *op, void *v, bool save, hipStream_t s)
-{
-  const NodeConstraints &nc = op->nc;
-  T                     *sv = save ? (T *)nc.d_save : nullptr;
-  if (op->dim == 2)
-    hipLaunchKernelGGL((k_nc_resolve<T, 2>), nc_grid(nc.n), dim3(NC_BLOCK), 0, s, (T *)v,
-                       nc.d_node, nc.d_comp, (const T *)nc.d_coef, sv, nc.n);
-  else
-    hipLaunchKernelGGL((k_nc_resolve<T, 3>), nc_grid(nc.n), dim3(NC_BLOCK), 0, s, (T *)v,
-                       nc.d_node, nc.d_comp, (const T *)nc.d_coef, sv, nc.n);
-  HIP_THROW(hipGetLastError());
-}
-
-template <typename T>
-void
-transpose_t(const glsOp_ *op, void *dst, void *src, bool zero, hipStream_t s)
-{
-  const NodeConstraints &nc = op->nc;
-  if (op->dim == 2)
-    hipLaunchKernelGGL((k_nc_transpose<T, 2>), nc_grid(nc.n), dim3(NC_BLOCK), 0, s, (T *)dst,
-                       (T *)src, nc.d_node, nc.d_comp, (const T *)nc.d_coef,
-                       (const T *)nc.d_save, nc.n, zero ? 1 : 0);
-  else
-    hipLaunchKernelGGL((k_nc_transpose<T, 3>), nc_grid(nc.n), dim3(NC_BLOCK), 0, s, (T *)dst,
-                       (T *)src, nc.d_node, nc.d_comp, (const T *)nc.d_coef,
-                       (const T *)nc.d_save, nc.n, zero ? 1 : 0);
-  HIP_THROW(hipGetLastError());
-}
-
-template <typename T>
-void
 diagonal_t(const glsOp_ *op, double *d64,
            void (*apply)(const glsOp_ *, void *, const void *, hipStream_t), hipStream_t s)
 {
@@ -422,10 +391,16 @@ nc_resolve(const glsOp_ *op, void *v, bool save, hipStream_t s)
 {
   if (op->nc.n == 0)
     return;
-  if (op->prec == GLS_F64)
-    resolve_t<double>(op, v, save, s);
-  else
-    resolve_t<float>(op, v, save, s);
+  const NodeConstraints &nc = op->nc;
+  with_real(op->prec, [&](auto t) {
+    using T = decltype(t);
+    with_int<2, 3>(op->dim, "node constraints", [&](auto d) {
+      hipLaunchKernelGGL((k_nc_resolve<T, decltype(d)::value>), nc_grid(nc.n), dim3(NC_BLOCK), 0,
+                         s, (T *)v, nc.d_node, nc.d_comp, (const T *)nc.d_coef,
+                         save ? (T *)nc.d_save : nullptr, nc.n);
+    });
+  });
+  HIP_THROW(hipGetLastError());
 }
 
 void
@@ -433,10 +408,16 @@ nc_transpose(const glsOp_ *op, void *dst, void *restore_src, bool zero, hipStrea
 {
   if (op->nc.n == 0)
     return;
-  if (op->prec == GLS_F64)
-    transpose_t<double>(op, dst, restore_src, zero, s);
-  else
-    transpose_t<float>(op, dst, restore_src, zero, s);
+  const NodeConstraints &nc = op->nc;
+  with_real(op->prec, [&](auto t) {
+    using T = decltype(t);
+    with_int<2, 3>(op->dim, "node constraints", [&](auto d) {
+      hipLaunchKernelGGL((k_nc_transpose<T, decltype(d)::value>), nc_grid(nc.n), dim3(NC_BLOCK),
+                         0, s, (T *)dst, (T *)restore_src, nc.d_node, nc.d_comp,
+                         (const T *)nc.d_coef, (const T *)nc.d_save, nc.n, zero ? 1 : 0);
+    });
+  });
+  HIP_THROW(hipGetLastError());
 }
 
 void
@@ -445,12 +426,11 @@ nc_restore(const glsOp_ *op, void *v, hipStream_t s)
   const NodeConstraints &nc = op->nc;
   if (nc.n == 0)
     return;
-  if (op->prec == GLS_F64)
-    hipLaunchKernelGGL(k_nc_restore<double>, nc_grid(nc.n), dim3(NC_BLOCK), 0, s, (double *)v,
-                       nc.d_node, nc.d_comp, (const double *)nc.d_save, nc.n, op->dim + 1);
-  else
-    hipLaunchKernelGGL(k_nc_restore<float>, nc_grid(nc.n), dim3(NC_BLOCK), 0, s, (float *)v,
-                       nc.d_node, nc.d_comp, (const float *)nc.d_save, nc.n, op->dim + 1);
+  with_real(op->prec, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(k_nc_restore<T>, nc_grid(nc.n), dim3(NC_BLOCK), 0, s, (T *)v, nc.d_node,
+                       nc.d_comp, (const T *)nc.d_save, nc.n, op->dim + 1);
+  });
   HIP_THROW(hipGetLastError());
 }
 
@@ -460,10 +440,7 @@ nc_diagonal(const glsOp_ *op, double *d64,
 {
   if (op->nc.n == 0)
     return;
-  if (op->prec == GLS_F64)
-    diagonal_t<double>(op, d64, apply, s);
-  else
-    diagonal_t<float>(op, d64, apply, s);
+  with_real(op->prec, [&](auto t) { diagonal_t<decltype(t)>(op, d64, apply, s); });
 }
 
 void
@@ -549,8 +526,9 @@ nc_check_values(const glsOp_ *op, const void *d_values, hipStream_t s)
         if ((op->h_cmask[(size_t)node] >> e) & 1)
           {
             const size_t dof = (size_t)node * nc + e;
-            const double v   = op->prec == GLS_F64 ? ((const double *)h.data())[dof] :
-                                                     (double)((const float *)h.data())[dof];
+            const double v   = with_real(op->prec, [&](auto t) {
+              return (double)((const decltype(t) *)h.data())[dof];
+            });
             if (v != 0.0)
               throw std::runtime_error(
                 "node constraints: a non-zero constraint value on component " +
@@ -623,11 +601,7 @@ gls_op_set_node_constraints(glsOp op, int64_t n, const int64_t *nodes, const int
           upload_vec(&nc.d_node, nc.h_node);
           upload_vec(&nc.d_comp, nc.h_comp);
           const size_t ts = op->tsize();
-          if (op->prec == GLS_F64)
-            upload_vec((double **)&nc.d_coef, nc.h_coef);
-          else
-            upload_vec((float **)&nc.d_coef,
-                       std::vector<float>(nc.h_coef.begin(), nc.h_coef.end()));
+          upload_real(op->prec, &nc.d_coef, nc.h_coef);
           HIP_THROW(hipMalloc(&nc.d_save, (size_t)n * ts));
           std::vector<int32_t> rows;
           colour_rows(op, rows);
@@ -688,14 +662,11 @@ gls_op_distribute(glsOp op, void *vec, int homogeneous, void *stream)
   const void *inhom = homogeneous ? nullptr : op->d_inhom;
   if (op->n_dofs > 0)
     {
-      if (op->prec == GLS_F64)
-        hipLaunchKernelGGL(k_nc_dirichlet<double>, nc_grid(op->n_dofs), dim3(NC_BLOCK), 0, s,
-                           (double *)v, op->d_node_cmask, (const double *)inhom, op->n_dofs,
-                           op->dim + 1);
-      else
-        hipLaunchKernelGGL(k_nc_dirichlet<float>, nc_grid(op->n_dofs), dim3(NC_BLOCK), 0, s,
-                           (float *)v, op->d_node_cmask, (const float *)inhom, op->n_dofs,
-                           op->dim + 1);
+      with_real(op->prec, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(k_nc_dirichlet<T>, nc_grid(op->n_dofs), dim3(NC_BLOCK), 0, s, (T *)v,
+                           op->d_node_cmask, (const T *)inhom, op->n_dofs, op->dim + 1);
+      });
       HIP_THROW(hipGetLastError());
     }
   nc_resolve(op, v, false, s);
@@ -703,12 +674,11 @@ gls_op_distribute(glsOp op, void *vec, int homogeneous, void *stream)
   if (op->n_slaves > 0)
     {
       const int64_t n = op->n_slaves * (op->dim + 1);
-      if (op->prec == GLS_F64)
-        hipLaunchKernelGGL(k_periodic_resolve<double>, nc_grid(n), dim3(NC_BLOCK), 0, s,
-                           (double *)v, op->d_slave_pairs, n, op->dim + 1);
-      else
-        hipLaunchKernelGGL(k_periodic_resolve<float>, nc_grid(n), dim3(NC_BLOCK), 0, s,
-                           (float *)v, op->d_slave_pairs, n, op->dim + 1);
+      with_real(op->prec, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(k_periodic_resolve<T>, nc_grid(n), dim3(NC_BLOCK), 0, s, (T *)v,
+                           op->d_slave_pairs, n, op->dim + 1);
+      });
       HIP_THROW(hipGetLastError());
     }
   op->stage.finish_out(vec, s);

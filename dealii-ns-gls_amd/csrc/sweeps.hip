@@ -11,25 +11,21 @@ namespace
 {
 using SweepKernel = void (*)(BrickArgs<float, 3, 3>, SweepArgs);
 
-template <int MODE, bool DET>
-SweepKernel
-sweep_kernel_m(int geo)
-{
-  if (geo == GEO_GEN)
-    return &k_brick_sweeps<3, 2, float, MODE, GEO_GEN, DET>;
-  if (geo == GEO_CART)
-    return &k_brick_sweeps<3, 2, float, MODE, GEO_CART, DET>;
-  return &k_brick_sweeps<3, 2, float, MODE, GEO_ANY, DET>;
-}
-
+// the instantiation of (mode, geometry, deterministic accumulation); nullptr
+// outside the two vmult modes
 SweepKernel
 sweep_kernel(int mode, int geo, bool det)
 {
-  if (mode == MODE_NEWTON)
-    return det ? sweep_kernel_m<MODE_NEWTON, true>(geo) : sweep_kernel_m<MODE_NEWTON, false>(geo);
-  if (mode == MODE_FIXED)
-    return det ? sweep_kernel_m<MODE_FIXED, true>(geo) : sweep_kernel_m<MODE_FIXED, false>(geo);
-  return nullptr;
+  if (mode != MODE_NEWTON && mode != MODE_FIXED)
+    return nullptr;
+  return with_int<MODE_NEWTON, MODE_FIXED>(mode, "resident sweeps", [&](auto m) {
+    return with_int<GEO_GEN, GEO_CART, GEO_ANY>(geo, "resident sweeps geometry", [&](auto g) {
+      return with_int<0, 1>(det, "resident sweeps", [&](auto d) -> SweepKernel {
+        return &k_brick_sweeps<3, 2, float, decltype(m)::value, decltype(g)::value,
+                               decltype(d)::value != 0>;
+      });
+    });
+  });
 }
 } // namespace
 
