@@ -1,6 +1,6 @@
 // arnoldi.h — what the three device GMRES solvers share beyond the kernels of
 // cgs.h: the single-domain CGS2 Arnoldi orthonormalisation (krylov.hip and the
-// coarse GMRES of mg.hip), the pipelined cycle and the restart loop (those two
+// coarse GMRES of coarse.hip), the pipelined cycle and the restart loop (those two
 // and the partitioned solver of dist_mg.hip), over the host least squares of
 // hessenberg.h.  A solver supplies a "space" (gls::GmresSpace of its own
 // callables, which keep their stream synchronisations):

@@ -1,6 +1,6 @@
 // cgs.h — Gram-Schmidt kernels of the device GMRES solvers: fused CGS2 passes
 // over the Krylov basis with per-block partials summed in a fixed order,
-// launched by cgs2_step of arnoldi.h (krylov.hip, the coarse GMRES of mg.hip)
+// launched by cgs2_step of arnoldi.h (krylov.hip, the coarse GMRES of coarse.hip)
 // and per member by dist_mg.hip; the delayed CGS2 kernels are krylov.hip's.
 #pragma once
 

@@ -74,6 +74,17 @@ upload_real(int prec, void **d, const std::vector<double> &h, bool alloc = true)
   });
 }
 
+// the 1-D grid of 256-thread workgroups over n items
+inline dim3
+g1(int64_t n)
+{
+  return dim3((unsigned)((n + 255) / 256));
+}
+
+// zero fill / copy of device buffers in 32-bit words, as kernels on s (mg.hip)
+void zero_words(void *x, int64_t n_words, hipStream_t s);
+void copy_words(void *y, const void *x, int64_t n_words, hipStream_t s);
+
 // what a brick launch runs: the brick kernel, and the shared-node reduction
 // of the owned rows, of the ghost rows (a partitioned operator's export
 // block), or of both

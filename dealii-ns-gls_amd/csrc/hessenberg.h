@@ -1,5 +1,5 @@
 // hessenberg.h — the host side of a GMRES cycle, shared by the three device
-// solvers (krylov.hip, mg.hip's coarse GMRES, dist_mg.hip): the least-squares
+// solvers (krylov.hip, coarse.hip's coarse GMRES, dist_mg.hip): the least-squares
 // problem min |g0 e_0 - H y| over the upper-Hessenberg matrix the Arnoldi
 // steps deliver column by column, by Givens rotations.  Plain C++17, no HIP
 // (tests/cpp/hessenberg_sanitize.cc compiles it alone).
