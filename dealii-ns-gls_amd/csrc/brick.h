@@ -200,6 +200,9 @@ struct BrickArgs
   T               nu4, stau2; // 4 nu, stau^2 (delta_qwise_fast)
   int             td, cw, have_prev, have_old_grad;
   int             det; // deterministic lattice accumulation (GLS_DETERMINISTIC): k_brick<..., DET>
+  // store policies of the write-out (kernels.h StorePolicy): STP_SLOT the
+  // partial-slot rows, STP_DST the exclusive dst and out64 rows
+  uint32_t        stp;
   Shape<T, n>     sh;
   // the coefficient tables' LDS image (S, S^T, Dq, Dq^T, rows padded to
   // CoefRow::RP values) in device memory, built once per operator
@@ -316,14 +319,21 @@ contract_v(const V *in, const T *tab, int pa, int base, int s)
 #ifndef GLS_TAB_FIRST
 #define GLS_TAB_FIRST 0
 #endif
-// Non-temporal stores of the brick write-out (dst rows and partial slots;
-// round 6 experiment): the 20 MB an r2 FP64 vmult writes stream out instead of
-// staying dirty in the L2s until the kernel's end.  Measured and NOT adopted
+// Store policy of the write-out and of the shared-node reduction (kernels.h
+// StorePolicy; BrickArgs::stp): plain, non-temporal or write-through 16-byte
+// stores, per store site, chosen per operator from GLS_STORE_POLICY when it
+// is created (gls_op.hip store_policy_of) -- no build switch.
+// Non-temporal (the former GLS_NT_STORE=1 build, round 6): NOT adopted
 // (profiles/r06/explore/ab_nt_store.txt): r2 FP64 33.0 -> 36.9 us, r3 FP64
-// 238 -> 345 us, FP32 r2 23.0 -> 24.0 us.  GLS_NT_STORE=1 builds it.
-#ifndef GLS_NT_STORE
-#define GLS_NT_STORE 0
-#endif
+// 238 -> 345 us, FP32 r2 23.0 -> 24.0 us; an nt store keeps its line in the
+// L2, it is not write-through.
+// Write-through (profiles/wt_store/README.md), r2 FP64: as it stands -- one
+// store instruction writing one 16-byte half of 64 different 32-byte rows --
+// slower, 32.2 -> 34.4 us on the slot rows alone; with the halves exchanged
+// between lane pairs so that each instruction writes whole rows
+// (store_rows_paired) and the reduction's rows written through, 32.1 ->
+// 31.6 us: the default of FP64 3D operators whose write-out fits the L2s
+// (gls_op.hip store_policy_of).  r3 and FP32 gain nothing and stay plain.
 
 template <int dim, int k, typename T>
 __host__ __device__ constexpr bool
@@ -910,11 +920,14 @@ __global__ void __launch_bounds__(256)
 // (build_bricks): the slots of node s of class (first, m, slot0) are
 // slot0 + (s - first) * m + [0, m), computed, not loaded, so the slot loads
 // issue together with the node id load (one memory round trip, not two).
-template <typename T, int nc, bool R>
+// stp: the store policy of the dst and out64 rows (STP_REDUCE; 16-byte
+// packs only: rows of other widths are stored plain).  LNT: the slot loads
+// non-temporal (each slot is read once).
+template <typename T, int nc, bool R, bool LNT = false>
 __global__ void __launch_bounds__(256)
   k_shared_reduce_cls(T *__restrict__ dst, const T *__restrict__ src,
                       const T *__restrict__ partial, const uint32_t *__restrict__ nodes,
-                      const ReduceClasses rc, int64_t n_shared,
+                      const ReduceClasses rc, int64_t n_shared, uint32_t stp,
                       const T *__restrict__ rb = nullptr, const T *__restrict__ rd = nullptr,
                       T romega = T(0), int keep = 1, uint32_t n_relax = 0xFFFFFFFFu,
                       double *__restrict__ out64 = nullptr)
@@ -940,22 +953,29 @@ __global__ void __launch_bounds__(256)
       const uint32_t b      = rc.slot0[k] + (s - rc.first[k]) * m;
       const uint32_t packed = nodes[s];
       const V       *pp     = reinterpret_cast<const V *>(partial) + kp;
+      auto           slot   = [&](uint32_t j) {
+        const V *q = pp + (size_t)(b + j) * NPK;
+        if constexpr (LNT)
+          return __builtin_nontemporal_load(q);
+        else
+          return *q;
+      };
       V              sum    = {};
       uint32_t       i      = 0;
       for (; i + 4 <= m; i += 4)
         {
-          const V x0 = pp[(size_t)(b + i) * NPK], x1 = pp[(size_t)(b + i + 1) * NPK];
-          const V x2 = pp[(size_t)(b + i + 2) * NPK], x3 = pp[(size_t)(b + i + 3) * NPK];
+          const V x0 = slot(i), x1 = slot(i + 1);
+          const V x2 = slot(i + 2), x3 = slot(i + 3);
           sum += (x0 + x1) + (x2 + x3);
         }
       if (i + 2 <= m)
         {
-          const V x0 = pp[(size_t)(b + i) * NPK], x1 = pp[(size_t)(b + i + 1) * NPK];
+          const V x0 = slot(i), x1 = slot(i + 1);
           sum += x0 + x1;
           i += 2;
         }
       if (i < m)
-        sum += pp[(size_t)(b + i) * NPK];
+        sum += slot(i);
       const uint32_t node = packed & NODE_MASK, cm = packed >> 28;
       if (cm)
 #pragma unroll
@@ -969,11 +989,18 @@ __global__ void __launch_bounds__(256)
           const V      dj = rd ? reinterpret_cast<const V *>(rd)[j] : V{} + T(1);
           sum = xs + romega * dj * (reinterpret_cast<const V *>(rb)[j] - sum);
         }
-      reinterpret_cast<V *>(dst)[(size_t)node * NPK + kp] = sum;
+      const int pol = store_policy(stp, STP_REDUCE);
+      store_pack<0>(reinterpret_cast<V *>(dst) + ((size_t)node * NPK + kp), sum, pol);
       if (out64)
-#pragma unroll
-        for (int w = 0; w < W; ++w)
-          out64[(size_t)node * nc + kp * W + w] = (double)sum[w];
+        {
+          // (FP32 rows: W = 4 values, two 16-byte packs of doubles)
+          typedef double D2 __attribute__((ext_vector_type(2)));
+          D2 *o = reinterpret_cast<D2 *>(out64 + (size_t)node * nc + kp * W);
+          static_assert(W == 2 || W == 4, "16-byte packs");
+          store_pack<0>(o, D2{(double)sum[0], (double)sum[1]}, pol);
+          if constexpr (W == 4)
+            store_pack<16>(o, D2{(double)sum[2], (double)sum[3]}, pol);
+        }
       return;
     }
   const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;

@@ -205,71 +205,87 @@
   __syncthreads();
 
   // ---- write out: exclusive nodes -> dst, boundary nodes -> partials
+  // FP64 rows under STORE_WT_ROWS: the lane keeps its row and the lane pairs
+  // store whole 32-byte rows together (store_rows_paired: every lane of the
+  // wavefront takes part, with a row or without)
+  constexpr bool PAIRS     = sizeof(T) == 8 && nc == 4;
+  const bool     rows_slot = PAIRS && store_policy(a.stp, STP_SLOT) == STORE_WT_ROWS; // (uniform)
+  const bool     rows_dst  = PAIRS && store_policy(a.stp, STP_DST) == STORE_WT_ROWS;
 #pragma unroll
   for (int it = 0; it < NI; ++it)
     {
-      const int i = t + it * BLOCK;
-      if (i >= L)
-        break;
-      const int      iz  = idiv_f(i, a.rLxy), iy = idiv_f(i - iz * Lxy, a.rLx);
-      const int      ip  = (i - iz * Lxy - iy * a.Lx) + a.PLx * (iy + a.PLy * iz);
+      const int      i   = t + it * BLOCK;
       const uint32_t tgt = tg[it];
-      if (tgt == UNUSED_NODE)
-        continue;
-      double acc[nc];
+      T              r[nc];
+      T             *row = nullptr;
+      if constexpr (PAIRS)
 #pragma unroll
-      for (int c = 0; c < nc; ++c)
-        acc[c] = s_acc[c * LP + ip];
-      T r[nc];
-      if (tgt & SHARED_BIT)
+        for (int c = 0; c < nc; ++c)
+          r[c] = T(0);
+      if (i < L && tgt != UNUSED_NODE)
         {
+          const int iz = idiv_f(i, a.rLxy), iy = idiv_f(i - iz * Lxy, a.rLx);
+          const int ip = (i - iz * Lxy - iy * a.Lx) + a.PLx * (iy + a.PLy * iz);
+          double    acc[nc];
 #pragma unroll
           for (int c = 0; c < nc; ++c)
-            r[c] = (T)(R ? -acc[c] : acc[c]);
-          if constexpr (GLS_NT_STORE && nc == 4)
-            store_node_nt<T>(a.partial, tgt & ~SHARED_BIT, r);
-          else
-            store_node<T, nc>(a.partial, tgt & ~SHARED_BIT, r);
-          continue;
-        }
-      const uint32_t cm = pk[it] >> 28;
-#pragma unroll
-      for (int c = 0; c < nc; ++c)
-        {
-          r[c] = (T)(R ? -acc[c] : acc[c]);
-          if ((cm >> c) & 1)
-            r[c] = R ? T(0) : (PRE ? xs[PRE ? it : 0][c] : a.src[(size_t)tgt * nc + c]);
-        }
-      if constexpr (PRE)
-        {
-          if (a.rb)
-#pragma unroll
-            for (int c = 0; c < nc; ++c)
-              {
-                const T base = a.rkeep ? xs[it][c] : T(0);
-                r[c]         = base + a.romega * xd[it][c] * (xb[it][c] - r[c]);
-              }
-        }
-      else if constexpr (!R)
-        if (a.rb)
-#pragma unroll
-          for (int c = 0; c < nc; ++c)
+            acc[c] = s_acc[c * LP + ip];
+          if (tgt & SHARED_BIT)
             {
-              const size_t j    = (size_t)tgt * nc + c;
-              const T      base = a.rkeep ? a.src[j] : T(0);
-              r[c]              = base + a.romega * (a.rd ? a.rd[j] : T(1)) * (a.rb[j] - r[c]);
-            }
-      if constexpr (GLS_NT_STORE && nc == 4)
-        store_node_nt<T>(a.dst, tgt, r);
-      else
-        store_node<T, nc>(a.dst, tgt, r);
-      if constexpr (sizeof(T) == 4 && !R)
-        if (a.out64)
-          {
-            double r64[nc];
 #pragma unroll
-            for (int c = 0; c < nc; ++c)
-              r64[c] = (double)r[c];
-            store_node<double, nc>(a.out64, tgt, r64);
-          }
+              for (int c = 0; c < nc; ++c)
+                r[c] = (T)(R ? -acc[c] : acc[c]);
+              if (rows_slot)
+                row = a.partial + (size_t)(tgt & ~SHARED_BIT) * nc;
+              else
+                store_node<T, nc>(a.partial, tgt & ~SHARED_BIT, r,
+                                  store_policy(a.stp, STP_SLOT));
+            }
+          else
+            {
+              const uint32_t cm = pk[it] >> 28;
+#pragma unroll
+              for (int c = 0; c < nc; ++c)
+                {
+                  r[c] = (T)(R ? -acc[c] : acc[c]);
+                  if ((cm >> c) & 1)
+                    r[c] = R ? T(0) : (PRE ? xs[PRE ? it : 0][c] : a.src[(size_t)tgt * nc + c]);
+                }
+              if constexpr (PRE)
+                {
+                  if (a.rb)
+#pragma unroll
+                    for (int c = 0; c < nc; ++c)
+                      {
+                        const T base = a.rkeep ? xs[it][c] : T(0);
+                        r[c]         = base + a.romega * xd[it][c] * (xb[it][c] - r[c]);
+                      }
+                }
+              else if constexpr (!R)
+                if (a.rb)
+#pragma unroll
+                  for (int c = 0; c < nc; ++c)
+                    {
+                      const size_t j    = (size_t)tgt * nc + c;
+                      const T      base = a.rkeep ? a.src[j] : T(0);
+                      r[c] = base + a.romega * (a.rd ? a.rd[j] : T(1)) * (a.rb[j] - r[c]);
+                    }
+              if (rows_dst)
+                row = a.dst + (size_t)tgt * nc;
+              else
+                store_node<T, nc>(a.dst, tgt, r, store_policy(a.stp, STP_DST));
+              if constexpr (sizeof(T) == 4 && !R)
+                if (a.out64)
+                  {
+                    double r64[nc];
+#pragma unroll
+                    for (int c = 0; c < nc; ++c)
+                      r64[c] = (double)r[c];
+                    store_node<double, nc>(a.out64, tgt, r64, store_policy(a.stp, STP_DST));
+                  }
+            }
+        }
+      if constexpr (PAIRS)
+        if (rows_slot || rows_dst)
+          store_rows_paired(row, r, (t & 1) != 0);
     }

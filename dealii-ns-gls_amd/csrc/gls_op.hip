@@ -130,6 +130,63 @@ op_cu_count(const glsOp_ *op)
   return n_cu;
 }
 
+// Store policies of a brick operator (kernels.h StorePolicy; BrickArgs::stp):
+// the defaults, or GLS_STORE_POLICY = three letters p (plain), n
+// (non-temporal) or w (write-through) for the partial-slot rows, the exclusive
+// dst / out64 rows of the brick write-out and the rows of the shared-node
+// reduction, and optionally a fourth, p or n, for the reduction's slot loads
+// ("wpw", "wwwn"); r: write-through with whole FP64 rows per instruction
+// (STORE_WT_ROWS; the two sites of the brick write-out, elsewhere w).  Read
+// when the operator is created, as GLS_TWO_LAYER is: one process can hold
+// operators with different policies.
+// Defaults (profiles/wt_store/README.md): FP64 3D operators whose write-out
+// -- partial-slot rows plus dst rows, `written_bytes` -- fits the eight XCD
+// L2s (32 MiB) write the brick write-out through as whole rows and the
+// reduction's rows through ("rrw"): those bytes would otherwise all stay
+// dirty in the L2s until the kernel's end and be written back in front of
+// the dependent launch (Re3900 r2: 12.4 MB, -0.5 us of 32.1).  Larger
+// operators (r3: 100 MB) evict their rows while the bricks still run, so
+// nothing waits at the boundary and write-through only gives up the L2's
+// write combining (r3: slower); FP32 rows gain nothing at either size.  Both
+// stay plain.
+uint32_t
+store_policy_of(const glsOp_ *op, size_t written_bytes)
+{
+  uint32_t    stp = 0;
+  const char *e   = getenv("GLS_STORE_POLICY");
+  if (!e || !e[0])
+    {
+      if (op->prec == GLS_F64 && op->dim == 3 && written_bytes <= ((size_t)32 << 20))
+        stp = (uint32_t)STORE_WT_ROWS << STP_SLOT | (uint32_t)STORE_WT_ROWS << STP_DST |
+              (uint32_t)STORE_WT << STP_REDUCE;
+      return stp;
+    }
+  const size_t len = strlen(e);
+  auto         bad = [&]() {
+    return std::runtime_error(std::string("GLS_STORE_POLICY=") + e +
+                              ": expected three of p, n, w, r and an optional p or n");
+  };
+  if (len != 3 && len != 4)
+    throw bad();
+  static constexpr int site[3] = {STP_SLOT, STP_DST, STP_REDUCE};
+  stp                          = 0;
+  for (int i = 0; i < 3; ++i)
+    {
+      const int pol = e[i] == 'p' ? STORE_PLAIN : e[i] == 'n' ? STORE_NT : e[i] == 'w' ? STORE_WT :
+                      e[i] == 'r' ? STORE_WT_ROWS : -1;
+      if (pol < 0)
+        throw bad();
+      stp |= (uint32_t)pol << site[i];
+    }
+  if (len == 4)
+    {
+      if (e[3] != 'p' && e[3] != 'n')
+        throw bad();
+      stp |= (e[3] == 'n' ? 1u : 0u) << STP_LOAD_NT;
+    }
+  return stp;
+}
+
 // Brick decomposition: node lattice per brick, exclusive vs shared nodes,
 // partial slots and the CSR that k_shared_reduce walks.
 void
@@ -466,7 +523,9 @@ build_bricks(glsOp_ *op, const glsOpDesc *d, const char *cell_curved)
   for (auto &v : shared_nodes)
     v |= (uint32_t)(d->node_cmask[v] & 0xF) << 28;
 
-  op->use_brick = true;
+  op->use_brick    = true;
+  op->store_policy =
+    store_policy_of(op, ((size_t)slot + (size_t)d->n_nodes) * (dim + 1) * op->tsize());
   op->bx = bx, op->by = by, op->bz = bz;
   op->L = L, op->Lx = Lx, op->Ly = Ly;
   op->n_bricks = nb;
@@ -913,6 +972,7 @@ struct Impl
     a.have_prev     = op->have_prev ? 1 : 0;
     a.have_old_grad = (op->have_old_grad && op->prm.theta != 1.0) ? 1 : 0;
     a.det           = (op->prm.flags & GLS_DETERMINISTIC) ? 1 : 0;
+    a.stp           = op->store_policy;
     a.sh            = make_shape<T, n>(op->basis);
     return a;
   }
@@ -995,15 +1055,20 @@ struct Impl
             const ReduceClasses &rc   = *rcp;
             const uint32_t      *nods = op->d_shared_nodes + r0;
             const uint32_t      *offs = op->d_shared_off + r0;
+            const int  lnt = (int)((a.stp >> STP_LOAD_NT) & 1u); // slot loads non-temporal
             if (rc.n > 0 && mode == MODE_RESIDUAL)
-              hipLaunchKernelGGL((k_shared_reduce_cls<T, dim + 1, true>), g3, dim3(256), 0, s,
-                                 (T *)dst, (const T *)src, (const T *)a.partial, nods, rc,
-                                 nr);
+              with_int<0, 1>(lnt, "shared-node reduction", [&](auto l) {
+                hipLaunchKernelGGL((k_shared_reduce_cls<T, dim + 1, true, decltype(l)::value != 0>),
+                                   g3, dim3(256), 0, s, (T *)dst, (const T *)src,
+                                   (const T *)a.partial, nods, rc, nr, a.stp);
+              });
             else if (rc.n > 0)
-              hipLaunchKernelGGL((k_shared_reduce_cls<T, dim + 1, false>), g3, dim3(256), 0, s,
-                                 (T *)dst, (const T *)src, (const T *)a.partial, nods, rc,
-                                 nr, a.rb, a.rd, a.romega, a.rkeep,
-                                 (uint32_t)op->n_owned_nodes, a.out64);
+              with_int<0, 1>(lnt, "shared-node reduction", [&](auto l) {
+                hipLaunchKernelGGL((k_shared_reduce_cls<T, dim + 1, false, decltype(l)::value != 0>),
+                                   g3, dim3(256), 0, s, (T *)dst, (const T *)src,
+                                   (const T *)a.partial, nods, rc, nr, a.stp, a.rb, a.rd,
+                                   a.romega, a.rkeep, (uint32_t)op->n_owned_nodes, a.out64);
+              });
             else if (mode == MODE_RESIDUAL)
               hipLaunchKernelGGL((k_shared_reduce<T, dim + 1, true>), g2, dim3(256), 0, s,
                                  (T *)dst, (const T *)src, (const T *)a.partial, nods, offs,

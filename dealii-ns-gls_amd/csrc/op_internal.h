@@ -231,6 +231,10 @@ struct glsOp_
   int64_t            n_shared_owned = 0;
   gls::ReduceClasses reduce_owned{}, reduce_ghost{};
   void     *d_partial      = nullptr;
+  // store policies of the brick write-out and the shared-node reduction
+  // (kernels.h StorePolicy, STP_* fields), fixed when the operator is created
+  // (gls_op.hip store_policy_of: the defaults, or GLS_STORE_POLICY)
+  uint32_t  store_policy   = 0;
   void     *d_bgeo_cart    = nullptr; // brick path: cell-indexed geometry
   void     *d_bgeo_gen     = nullptr;
   // per brick, one 16-byte record (gls::BrickRec: first cell, first table
