@@ -274,6 +274,58 @@ contract_v(const V *in, const T *tab, int pa, int base, int s)
   return contract_c<n>(in, c, base, s);
 }
 
+// Batched stages (GLS_STAGE_BATCH, brick_rounds.inc): a stage's coefficient
+// row and the lines of every pack are read into named registers ahead of a
+// scheduling barrier and consumed behind it in the order of issue, so the
+// reads leave back to back and the compiler's counted lgkmcnt waits pipeline
+// them (LDS returns in order) -- instead of read 2-4, drain, two FMAs, read
+// 1, drain as the register allocator orders them at the 4-wave budget.  The
+// FMA chains are contract_c's, term by term: results are bitwise the same.
+template <int n, int NP, typename V>
+__device__ __forceinline__ void
+read_lines(const V *in, int pstride, int base, int s, V (&d)[NP][n])
+{
+#pragma unroll
+  for (int kp = 0; kp < NP; ++kp)
+#pragma unroll
+    for (int j = 0; j < n; ++j)
+      d[kp][j] = in[kp * pstride + base + j * s];
+}
+
+template <int n, typename T, typename V>
+__device__ __forceinline__ V
+contract_r(const T (&c)[n], const V (&d)[n])
+{
+  V acc = c[0] * d[0];
+#pragma unroll
+  for (int j = 1; j < n; ++j)
+    acc += c[j] * d[j];
+  return acc;
+}
+
+// one sweep's contraction of every pack with the coefficient row c (read by
+// the caller just before): batched, or pack by pack as contract_c
+template <bool BATCH, int n, int NP, typename T, typename V>
+__device__ __forceinline__ void
+contract_packs(const V *in, int pstride, const T (&c)[n], int base, int s, V (&r)[NP])
+{
+  if constexpr (BATCH)
+    {
+      V d[NP][n];
+      read_lines<n, NP>(in, pstride, base, s, d);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int kp = 0; kp < NP; ++kp)
+        r[kp] = contract_r<n>(c, d[kp]);
+    }
+  else
+    {
+#pragma unroll
+      for (int kp = 0; kp < NP; ++kp)
+        r[kp] = contract_c<n>(in + kp * pstride, c, base, s);
+    }
+}
+
 // x contractions across lanes (3D Q2, round 6).  The lanes of a wavefront
 // hold 18 x-lines of 3 quadrature points (2 cells x 9 lines), five lines per
 // 16-lane DPP row (lane 16 r + 3 s + x; the 16th lane of every row and the
@@ -319,6 +371,24 @@ contract_v(const V *in, const T *tab, int pa, int base, int s)
 #ifndef GLS_TAB_FIRST
 #define GLS_TAB_FIRST 0
 #endif
+// Batched LDS reads of the cell rounds' stages (read_lines / contract_r), a
+// bitmask of stages for A/B builds: 1 the collocation gradient, 2 the first
+// Dq^T exchange, 4 the x S^T sweep in front of the lattice accumulation, 8
+// the two-pack S / S^T sweeps.  Default 9: the gradient (-0.7 us on the FP64
+// r2 vmult) and the sweeps (another -0.3 us on top of it); the x S^T batch
+// adds nothing measurable alone or with them, and the Dq^T exchange excludes
+// the gradient (stage_batch below).  Which instantiations take which form:
+// stage_batch; measurements: profiles/stage_batch/README.md.
+#ifndef GLS_STAGE_BATCH
+#define GLS_STAGE_BATCH 9
+#endif
+enum
+{
+  SB_GRAD  = 1,
+  SB_DQT   = 2,
+  SB_XST   = 4,
+  SB_SWEEP = 8
+};
 // Store policy of the write-out and of the shared-node reduction (kernels.h
 // StorePolicy; BrickArgs::stp): plain, non-temporal or write-through 16-byte
 // stores, per store site, chosen per operator from GLS_STORE_POLICY when it
@@ -751,6 +821,47 @@ struct BrickOcc
                                                          (X ? GLS_XD_WAVES_F64 : 4)) :
                                        (sizeof(T) == 4 ? 4 : 3);
 };
+
+// The batched stages (GLS_STAGE_BATCH) of one instantiation of the cell
+// rounds.
+template <int dim, int k, typename T, int MODE, int GEO, int ZL>
+__host__ __device__ constexpr int
+stage_batch()
+{
+  // the 3D Q2 one-layer vmult kernels only (BrickOcc::four): in the 2D,
+  // degree-1 and -3, two-layer and residual instantiations a batch costs a
+  // wave by the register count or spills
+  if (xdpp<dim, k, T>() || !BrickOcc<dim, k, T, MODE, GEO, ZL>::four)
+    return 0;
+  // FP64 only: the FP32 kernels (5 waves, one pack) keep their registers and
+  // waves with the batches but gain no time (bench --precision f32 level,
+  // V-cycle and GMRES iteration level or 1-2 % slower), and with the Dq^T
+  // exchange batched the compiler fuses the products around it into other
+  // FMAs: deterministic results are then no longer bitwise the unbatched ones
+  if (sizeof(T) != 8)
+    return 0;
+  int m = GLS_STAGE_BATCH;
+  // the Dq^T exchange: Newton kernels only (the fixed-point kernels would
+  // lose a wave by the register count)
+  if (MODE != MODE_NEWTON)
+    m &= ~SB_DQT;
+  // with the gradient and the Dq^T exchange both batched the compiler no
+  // longer peels the round loop's first iteration (the Cartesian body's
+  // `base > 0` loads) and the headline kernel spills 152 B/lane: the
+  // gradient takes precedence
+  if (m & SB_GRAD)
+    m &= ~SB_DQT;
+  return m;
+}
+// the gradient stage's batches: one pack's lines where a whole axis's do not
+// fit the registers (the stand-alone GEO_CART FP64 kernels: 20 B/lane of
+// scratch with whole axes)
+template <typename T, int GEO>
+__host__ __device__ constexpr bool
+grad_by_pack()
+{
+  return sizeof(T) == 8 && GEO == GEO_CART;
+}
 
 // DET: the deterministic lattice accumulation (GLS_DETERMINISTIC: the cells
 // of a round add in cell order between barriers instead of by LDS atomics;

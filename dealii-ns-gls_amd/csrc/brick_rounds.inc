@@ -25,6 +25,10 @@
     // prefetch the next round's behind the Dq^T sweeps
     constexpr bool LATE  = FOUR && G == GEO_CART;
     constexpr bool ATUSE = FOUR && G == GEO_GEN;
+    // the stages whose LDS reads are issued as batches (brick.h stage_batch)
+    constexpr int  SBM   = stage_batch<dim, k, T, MODE, GEO, ZL>();
+    // the gradient's batches: one pack's lines instead of a whole axis's
+    [[maybe_unused]] constexpr bool GRAD_PACK = grad_by_pack<T, GEO>();
     for (int base = 0; base < ncell; base += step)
       {
         if (LATE && base > 0)
@@ -58,9 +62,7 @@
             T c[n];
             coefs<n>(sS, pa[0], c);
             V r[NP];
-#pragma unroll
-            for (int kp = 0; kp < NP; ++kp)
-              r[kp] = contract_c<n>(s_src + kp * LP, c, li - pa[0], 1);
+            contract_packs<(SBM & SB_SWEEP) != 0, n>(s_src, LP, c, li - pa[0], 1, r);
 #pragma unroll
             for (int kp = 0; kp < NP; ++kp)
               A[kp * BL::KS + q] = r[kp];
@@ -75,9 +77,8 @@
                 T c[n];
                 coefs<n>(sS, pa[ax], c);
                 V r[NP];
-#pragma unroll
-                for (int kp = 0; kp < NP; ++kp)
-                  r[kp] = contract_c<n>(in + kp * BL::KS, c, q - pa[ax] * st[ax], st[ax]);
+                contract_packs<(SBM & SB_SWEEP) != 0, n>(in, BL::KS, c, q - pa[ax] * st[ax],
+                                                         st[ax], r);
 #pragma unroll
                 for (int kp = 0; kp < NP; ++kp)
                   out[kp * BL::KS + q] = r[kp];
@@ -125,6 +126,57 @@
                       for (int ax = 0; ax < dim; ++ax)
                         gref[kp * W + w][ax] = g[ax][w];
                     }
+              }
+          }
+        else if constexpr ((SBM & SB_GRAD) != 0)
+          {
+            // batched: the values, then per axis the Dq row and the lines of
+            // every pack (or of one pack at a time, GRAD_PACK) in one batch
+            if (in_wave)
+              {
+                V v[NP], g[NP][dim];
+#pragma unroll
+                for (int kp = 0; kp < NP; ++kp)
+                  v[kp] = in[kp * BL::KS + q];
+#pragma unroll
+                for (int ax = 0; ax < dim; ++ax)
+                  {
+                    T c[n];
+                    coefs<n>(sD, pa[ax], c);
+                    if constexpr (GRAD_PACK)
+                      {
+#pragma unroll
+                        for (int kp = 0; kp < NP; ++kp)
+                          {
+                            V d[1][n];
+                            read_lines<n, 1>(in + kp * BL::KS, 0, q - pa[ax] * st[ax], st[ax], d);
+                            __builtin_amdgcn_sched_barrier(0);
+                            g[kp][ax] = contract_r<n>(c, d[0]);
+                            __builtin_amdgcn_sched_barrier(0);
+                          }
+                      }
+                    else
+                      {
+                        V d[NP][n];
+                        read_lines<n, NP>(in, BL::KS, q - pa[ax] * st[ax], st[ax], d);
+                        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                        for (int kp = 0; kp < NP; ++kp)
+                          g[kp][ax] = contract_r<n>(c, d[kp]);
+                        __builtin_amdgcn_sched_barrier(0);
+                      }
+                  }
+#pragma unroll
+                for (int kp = 0; kp < NP; ++kp)
+#pragma unroll
+                  for (int w = 0; w < W; ++w)
+                    if (kp * W + w < nc)
+                      {
+                        val[kp * W + w] = v[kp][w];
+#pragma unroll
+                        for (int ax = 0; ax < dim; ++ax)
+                          gref[kp * W + w][ax] = g[kp][ax][w];
+                      }
               }
           }
         else if (in_wave)
@@ -350,7 +402,33 @@
                   }
               }
             wave_sync();
-            if (in_wave)
+            // batched (A/B builds only: no default kernel takes this path,
+            // brick.h stage_batch): both axes' Dq^T rows and lines, A's then
+            // B's, each pack's terms in the order of the unbatched form
+            bool batched = false;
+            if constexpr ((SBM & SB_DQT) != 0)
+              if (ax0 + 1 < dim)
+                {
+                  batched = true;
+                  if (in_wave)
+                    {
+                      const int ax1 = (ax0 + 1) % dim;
+                      T         c0[n], c1[n];
+                      V         d0[NP][n], d1[NP][n];
+                      coefs<n>(sDT, pa[ax0], c0);
+                      read_lines<n, NP>(A, BL::KS, q - pa[ax0] * st[ax0], st[ax0], d0);
+                      coefs<n>(sDT, pa[ax1], c1);
+                      read_lines<n, NP>(B, BL::KS, q - pa[ax1] * st[ax1], st[ax1], d1);
+                      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                      for (int kp = 0; kp < NP; ++kp)
+                        wv[kp] += contract_r<n>(c0, d0[kp]);
+#pragma unroll
+                      for (int kp = 0; kp < NP; ++kp)
+                        wv[kp] += contract_r<n>(c1, d1[kp]);
+                    }
+                }
+            if (!batched && in_wave)
 #pragma unroll
               for (int kp = 0; kp < NP; ++kp)
                 {
@@ -416,9 +494,8 @@
                 T c[n];
                 coefs<n>(sST, pa[ax], c);
                 V r[NP];
-#pragma unroll
-                for (int kp = 0; kp < NP; ++kp)
-                  r[kp] = contract_c<n>(in + kp * BL::KS, c, q - pa[ax] * st[ax], st[ax]);
+                contract_packs<(SBM & SB_SWEEP) != 0, n>(in, BL::KS, c, q - pa[ax] * st[ax],
+                                                         st[ax], r);
 #pragma unroll
                 for (int kp = 0; kp < NP; ++kp)
                   out[kp * BL::KS + q] = r[kp];
@@ -452,6 +529,22 @@
                     }
               }
             __syncthreads();
+          }
+        else if constexpr (!XD && (SBM & SB_XST) != 0)
+          {
+            // batched: the row (above) and both packs' lines before the first
+            // ds_add (an LDS atomic orders every later LDS read behind it)
+            if (active_now)
+              {
+                V r[NP];
+                contract_packs<true, n>(in, BL::KS, cx, q - pa[0], 1, r);
+#pragma unroll
+                for (int kp = 0; kp < NP; ++kp)
+#pragma unroll
+                  for (int w = 0; w < W; ++w)
+                    if (kp * W + w < nc)
+                      lds_add(s_acc + (kp * W + w) * LP + li_now, (double)r[kp][w]);
+              }
           }
         else if (active_now)
 #pragma unroll
